@@ -4,12 +4,17 @@
 A "step" is one whole `odeint` call.  Default = config 4: linear f(t, y) = A y, dim 128, Dopri5,
 float64, rtol 1e-6, atol 1e-9, t = [0, 1]; inputs resident in HBM before the timed region.  ONE JSON line on stdout.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--config 1..5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--config 1..5] [--dump-outputs DIR]
     python bench.py --config published [--published-all]     # the reference's own published workloads, one line each
 
+--dump-outputs DIR: after the timed steps, the solution the LAST timed step returned is written as DIR/solution.npy
+(DIR/solution_rank<r>.npy per rank when N > 1) in the step's own dtype, [len(t), rows, dim].  The files hold at most DUMP_MAX_BYTES (32 MiB) in all:
+a larger solution is cut to a fixed sample of rows (trajectories) drawn with seed DUMP_SEED, sorted, every output time and
+state component kept.  The inputs are seeded, so two builds run with the same arguments can be compared file for file.
+
 N > 1: one process per GPU over RCCL.  Launched by the driver as `python -m torch.distributed.run ... bench.py --gpus N`
-(RANK / WORLD_SIZE in the environment); a bare `python bench.py --gpus N` re-executes itself under
-torch.distributed.run with N ranks.  The line is refused (exit 2) if the ranks that ran differ from --gpus.
+(RANK / WORLD_SIZE in the environment); a bare `python bench.py --gpus N` runs itself under
+torch.distributed.run with N ranks, as a child process.  The line is refused (exit 2) if the ranks that ran differ from --gpus.
   --scaling weak   (default) 65536 rows PER GPU; value = N x 65536 x 128 x steps / wall
   --scaling strong the fixed 65536 x 128 batch of BASELINE config 4 sharded N ways (N = 1: the same run as weak)
 The documented pair for a multi-GPU node is `--gpus N` (weak, what the driver runs) and `--gpus N --scaling strong`.
@@ -57,6 +62,8 @@ FP32_MFMA_PEAK_TFLOPS = 157.3    # MI355X_MICROARCH.md: fp32-input MFMA = the fp
 NOMINAL_CLOCK_MHZ = 2400.0       # the engine clock both peaks are quoted at
 CPU_LEG_BUDGET_S = 10.0
 CPU_PLAN = ((8, 3), (32, 2), (1, 1))    # (pinned threads, timed runs after one warm-up) of the CPU baseline, full shard each
+DUMP_MAX_BYTES = 32 << 20        # --dump-outputs: bytes written over all ranks (the contract's ceiling is 64 MB)
+DUMP_SEED = 0                    # --dump-outputs: seed of the row sample of a solution over DUMP_MAX_BYTES
 
 
 class Hwmon(object):
@@ -159,6 +166,22 @@ def config4(batch, dim, seed_y):
     g3 = torch.Generator().manual_seed(seed_y)
     y0 = torch.randn(batch, dim, generator=g3, dtype=torch.float64)
     return A, y0
+
+
+def dump_outputs(dirname, sol, rank, world):
+    """--dump-outputs: `sol` ([len(t), rows, dim], on the device) as DIR/solution.npy, or a fixed, seeded sample of its rows when the whole
+    solution would exceed this rank's share of DUMP_MAX_BYTES.  Returns what was written, for the result line."""
+    rows = int(sol.shape[1])
+    row_bytes = sol[:, 0].numel() * sol.element_size()
+    keep = min(rows, (DUMP_MAX_BYTES // world) // row_bytes)
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+        sol = sol.index_select(1, torch.from_numpy(idx).to(sol.device))
+    name = 'solution' if world == 1 else 'solution_rank%d' % rank
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + '.npy'), sol.detach().cpu().numpy())
+    return {'file': name + '.npy', 'shape': list(sol.shape), 'dtype': str(sol.dtype).replace('torch.', ''),
+            'rows': 'all' if keep == rows else 'sample of %d of %d rows, seed %d' % (keep, rows, DUMP_SEED)}
 
 
 def cpu_model():
@@ -286,8 +309,10 @@ def cpu_baseline(gpu_result):
 
 
 def respawn(args):
-    """`python bench.py --gpus N` without a launcher: become `torch.distributed.run --nproc-per-node N bench.py ...`."""
+    """`python bench.py --gpus N` without a launcher: run `torch.distributed.run --nproc-per-node N bench.py ...` as a child process and exit
+    with its status (a child, not exec: this process has initialised the HIP runtime already)."""
     import socket
+    import subprocess
     n_dev = torch.cuda.device_count()
     if n_dev < args.gpus:
         sys.stderr.write('bench.py: --gpus %d but only %d GPU(s) are visible; refusing to report an N-GPU number\n' % (args.gpus, n_dev))
@@ -299,7 +324,8 @@ def respawn(args):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.gpus), '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0'))
-    os.execvpe(cmd[0], cmd, env)
+    sys.stdout.flush()
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def workload(cfg, args, rank, world, dev):
@@ -435,8 +461,14 @@ def main():
     ap.add_argument('--fusion', default='auto', choices=['auto', 'stage', 'step', 'whole'],
                     help="'stage': one kernel per RK stage (34 planes/attempt, HBM-bound); 'step': whole attempt in one kernel; "
                          "'whole'/'auto': the whole call in one launch")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='configs 1-5: write the solution of the last timed step to DIR (see the module docstring)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     if args.config == 'published':
+        if args.dump_outputs:
+            ap.error('--dump-outputs applies to configs 1-5, not to --config published')
         published(args)
         return
     args.config = int(args.config)
@@ -573,6 +605,7 @@ def main():
     smi['after_timed_steps'] = hw.read()                      # (six file reads, ~0.5 ms: after the clock is stopped)
     if gc_was_enabled:
         gc.enable()
+    dumped = dump_outputs(args.dump_outputs, out, rank, world) if args.dump_outputs else None
     per_rank = None
     if use_dist:
         el = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -795,6 +828,8 @@ def main():
         }
         if stage_roof is not None:
             res['roofline_per_stage_schedule'] = stage_roof
+        if dumped is not None:
+            res['dumped_outputs'] = dict(dumped, dir=args.dump_outputs)
         # The pool's boxes grant the kernels that keep every matrix pipe busy different clocks (2122 ... 2398 MHz seen for the same
         # binary, profiles/r04_clock_variation.txt); `frac` stays what the contract defines (against the nominal peak at 2400 MHz),
         # this is the same figure against the peak at the clock THIS run was granted (counted by the kernel itself)

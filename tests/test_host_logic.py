@@ -385,6 +385,26 @@ def test_bench_refuses_more_ranks_than_devices_with_one_line():
     assert len(lines) == 1 and '--gpus 2' in lines[0] and 'device(s) visible' in lines[0]
 
 
+def test_bench_dump_outputs_is_a_fixed_sample_within_the_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: a solution over the byte budget is cut to the same sorted, seeded rows on every call (two builds compare
+    file for file), every output time and component kept; a small one is written whole; N ranks share the budget."""
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 4096)
+    sol = torch.arange(2 * 100 * 8, dtype=torch.float64).reshape(2, 100, 8)          # 128 bytes per row: 32 rows fit
+    a = bench.dump_outputs(str(tmp_path / 'a'), sol, 0, 1)
+    b = bench.dump_outputs(str(tmp_path / 'b'), sol, 0, 1)
+    xa, xb = np.load(str(tmp_path / 'a' / 'solution.npy')), np.load(str(tmp_path / 'b' / 'solution.npy'))
+    assert a == b and a['shape'] == [2, 32, 8] and a['dtype'] == 'float64' and np.array_equal(xa, xb)
+    assert xa.nbytes <= bench.DUMP_MAX_BYTES
+    rows = xa[0, :, 0] / 8
+    assert np.all(np.diff(rows) > 0) and np.array_equal(xa, sol.numpy()[:, rows.astype(np.int64)])
+    small = torch.ones(3, 5, 4, dtype=torch.float32)
+    assert bench.dump_outputs(str(tmp_path / 'c'), small, 0, 1)['rows'] == 'all'
+    assert np.array_equal(np.load(str(tmp_path / 'c' / 'solution.npy')), small.numpy())
+    r1 = bench.dump_outputs(str(tmp_path / 'd'), sol, 1, 2)
+    assert r1['file'] == 'solution_rank1.npy' and r1['shape'] == [2, 16, 8]
+
+
 def test_a_users_own_time_reversed_attribute_is_not_taken_for_the_native_hook():
     """(advisor, round 4) only the private `_mi_time_reversed` is the hook; a user's callable that happens to have a `time_reversed` attribute is
     wrapped like any other."""
