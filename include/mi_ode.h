@@ -510,6 +510,52 @@ int mi_ode_interp_eval(int32_t dtype, int32_t interp, int64_t n, const void* y0_
                        const void* const* ks_dev, int32_t nk, const double* c_mid, double dt, double t0, double t1,
                        double t, void* out_dev, void* stream);
 
+/* ---- (D) hypersolvers (tfdiffeq/hyper_solvers/: HyperEuler, HyperMidpoint, HyperHeun) ------------------------------------
+ * A fixed step of the base method plus dt^(p+1) * g(cat([y, f(t, y), dt])), g a dense network given as a layer table; euler.py's
+ * formulas literally (dt = t[1] - t[0] for every step, row i of a trajectory = the state before step i).  One call = the whole
+ * trajectory / residual computation: csrc/mi_ode_hyper.h.  f: a row-local catalogue system (LORENZ, LOTKA_VOLTERRA, the dim-2
+ * LINEAR / CUBIC_LINEAR with W by value in scalars[0..3]) or MI_ODE_RHS_PLUGIN with `plugin` = what a hyper plugin's
+ * mi_ode_hyper_plugin_get(dtype) returned (csrc/mi_ode_hyper_plugin.h). */
+#define MI_ODE_HYPER_MAX_LAYERS 6
+#define MI_ODE_HYPER_WORKSPACE_BYTES (1 << 20)    /* device workspace a call may use for g's packed weights */
+enum mi_ode_hyper_method { MI_ODE_HYPER_EULER = 0, MI_ODE_HYPER_MIDPOINT = 1, MI_ODE_HYPER_HEUN = 2 };
+enum mi_ode_hyper_mode {
+  MI_ODE_HYPER_TRAJECTORY = 0,   /* trajectory(t_span, y): out [T, batch, dim] from y [batch, dim]                          */
+  MI_ODE_HYPER_RESIDUAL = 1,     /* residual_trajectory(t_span, base) of HyperEuler: out [T - 1, batch, dim] from y [T, batch, dim] */
+  MI_ODE_HYPER_G_RESIDUALS = 2   /* _hypersolver_residuals(t_span, base): out [T, batch, dim] from y [T, batch, dim]           */
+};
+enum mi_ode_hyper_act {
+  MI_ODE_HYPER_ACT_NONE = 0, MI_ODE_HYPER_ACT_RELU = 1, MI_ODE_HYPER_ACT_LEAKY_RELU = 2, MI_ODE_HYPER_ACT_PRELU = 3,
+  MI_ODE_HYPER_ACT_TANH = 4, MI_ODE_HYPER_ACT_SOFTPLUS = 5     /* softplus: beta 1, threshold 20 */
+};
+typedef struct mi_ode_hyper_layer {
+  int32_t in, out;            /* nn.Linear(in, out); widths <= 128 */
+  int32_t act;                /* enum mi_ode_hyper_act: the activation that follows the layer */
+  int32_t n_alpha;            /* PReLU: 1 (shared) or out (per channel) */
+  double slope;               /* LeakyReLU negative slope */
+  const void* w;              /* device, state dtype: [out, in] row-major (nn.Linear.weight) */
+  const void* b;              /* device, nullable: [out] */
+  const void* alpha;          /* device, PReLU only: [n_alpha] */
+} mi_ode_hyper_layer;
+typedef struct mi_ode_hyper {
+  int32_t dtype;              /* enum mi_ode_dtype */
+  int32_t method;             /* enum mi_ode_hyper_method */
+  int32_t mode;               /* enum mi_ode_hyper_mode */
+  int32_t n_layers;           /* 2 .. MI_ODE_HYPER_MAX_LAYERS; layers[0].in = 2 dim + 1, layers[n - 1].out = dim */
+  int64_t batch, dim;
+  int32_t T;                  /* time points, >= 2 */
+  int32_t reserved;
+  const void* t;              /* device [T], state dtype */
+  const void* y;              /* device: y0 [batch, dim] (TRAJECTORY) or the base trajectory [T, batch, dim] */
+  void* out;                  /* device, see enum mi_ode_hyper_mode */
+  void* workspace;            /* device, MI_ODE_HYPER_WORKSPACE_BYTES: g's packed weights when they do not fit in LDS */
+  mi_ode_rhs rhs;             /* f */
+  mi_ode_hyper_layer layers[MI_ODE_HYPER_MAX_LAYERS];
+} mi_ode_hyper;
+/* Enqueues the call on `stream`.  Returns the number of kernel launches it enqueued (1, or 2 when g's weights are packed to the
+ * workspace first), or a negative MI_ODE_E_*. */
+int mi_ode_hyper_run(const mi_ode_hyper* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

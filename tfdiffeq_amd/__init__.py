@@ -9,6 +9,7 @@ from .odeint import odeint, SOLVERS
 from .adjoint import odeint_adjoint
 from .misc import move_to_device
 from . import rhs
+from . import hyper_solvers
 from .solvers import clear_engine_cache
 
 __all__ = ['odeint', 'odeint_adjoint', 'SOLVERS', 'move_to_device', 'rhs', 'clear_engine_cache']

@@ -99,6 +99,27 @@ class OpqDesc(C.Structure):
                 ('safety', C.c_double), ('ifactor', C.c_double), ('dfactor', C.c_double), ('max_num_steps', C.c_int64)]
 
 
+HYPER_MAX_LAYERS = 6
+HYPER_WORKSPACE_BYTES = 1 << 20
+HYPER_EULER, HYPER_MIDPOINT, HYPER_HEUN = 0, 1, 2
+HYPER_TRAJECTORY, HYPER_RESIDUAL, HYPER_G_RESIDUALS = 0, 1, 2
+HYPER_ACT_NONE, HYPER_ACT_RELU, HYPER_ACT_LEAKY_RELU, HYPER_ACT_PRELU, HYPER_ACT_TANH, HYPER_ACT_SOFTPLUS = 0, 1, 2, 3, 4, 5
+
+
+class HyperLayer(C.Structure):
+    """mi_ode_hyper_layer: one nn.Linear of a hypersolver's g and the activation after it."""
+    _fields_ = [('in_', C.c_int32), ('out', C.c_int32), ('act', C.c_int32), ('n_alpha', C.c_int32), ('slope', C.c_double),
+                ('w', C.c_void_p), ('b', C.c_void_p), ('alpha', C.c_void_p)]
+
+
+class HyperDesc(C.Structure):
+    """mi_ode_hyper: a hypersolver trajectory / residual call in one launch (include/mi_ode.h section D)."""
+    _fields_ = [('dtype', C.c_int32), ('method', C.c_int32), ('mode', C.c_int32), ('n_layers', C.c_int32),
+                ('batch', C.c_int64), ('dim', C.c_int64), ('T', C.c_int32), ('reserved', C.c_int32),
+                ('t', C.c_void_p), ('y', C.c_void_p), ('out', C.c_void_p), ('workspace', C.c_void_p),
+                ('rhs', Rhs), ('layers', HyperLayer * HYPER_MAX_LAYERS)]
+
+
 class Stats(C.Structure):
     _fields_ = [('n_attempts', C.c_int64), ('n_accepted', C.c_int64), ('n_rejected', C.c_int64), ('nfe', C.c_int64),
                 ('t', C.c_double), ('dt', C.c_double), ('last_ratio', C.c_double),
@@ -190,6 +211,7 @@ _PROTOS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     'mi_ode_adams_update_phi': (C.c_int, [C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_double),
                                           C.POINTER(C.c_void_p), C.c_void_p]),
+    'mi_ode_hyper_run': (C.c_int, [C.POINTER(HyperDesc), C.c_void_p]),
     'mi_ode_interp_eval': (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                      C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double,
                                      C.c_double, C.c_void_p, C.c_void_p]),

@@ -45,12 +45,13 @@ def plugin_dir():
     return d
 
 
-def _plugin_headers():
-    """The headers a plugin translation unit actually sees: the #include closure of mi_ode_plugin.h inside csrc/ and include/ (a change to
-    the MLP / adjoint / linear-adjoint kernels does not invalidate the cache of compiled right-hand sides)."""
+def _plugin_headers(roots=('mi_ode_plugin.h',)):
+    """The headers a plugin translation unit actually sees: the #include closure of its own includes (mi_ode_plugin.h, or
+    mi_ode_hyper_plugin.h for a hyper plugin) inside csrc/ and include/ (a change to the MLP / adjoint / linear-adjoint kernels does not
+    invalidate the cache of compiled right-hand sides)."""
     import re
     inc = os.path.join(os.path.dirname(N.CSRC.rstrip(os.sep).rsplit(os.sep, 1)[0]), 'include')
-    seen, todo = [], ['mi_ode_plugin.h']
+    seen, todo = [], list(roots)
     while todo:
         name = todo.pop()
         for d in (N.CSRC, inc):
@@ -63,9 +64,14 @@ def _plugin_headers():
     return sorted(seen)
 
 
-def _headers_digest():
+def _source_roots(source):
+    import re
+    return tuple(re.findall(r'^\s*#\s*include\s*"([^"]+)"', source, flags=re.M)) or ('mi_ode_plugin.h',)
+
+
+def _headers_digest(roots=('mi_ode_plugin.h',)):
     h = hashlib.sha256()
-    for path in _plugin_headers():
+    for path in _plugin_headers(roots):
         with open(path, 'rb') as fh:
             h.update(fh.read())
     return h.hexdigest()
@@ -75,7 +81,7 @@ def build(source, verbose=False):
     """Path of the compiled plugin for `source` (compiles on a cache miss; the key covers the kernel headers too)."""
     # (the include directories are NOT part of the key - their content is, through _headers_digest: a checkout that was moved, or copied to
     # another machine with its in-tree plugin cache, keeps hitting it)
-    key = hashlib.sha256((source + _headers_digest() + ' '.join(f for f in FLAGS if not os.path.isabs(f))).encode()).hexdigest()[:24]
+    key = hashlib.sha256((source + _headers_digest(_source_roots(source)) + ' '.join(f for f in FLAGS if not os.path.isabs(f))).encode()).hexdigest()[:24]
     out = os.path.join(plugin_dir(), 'rhs_%s.so' % key)
     if os.path.exists(out):
         if not _owned_private(out):
@@ -110,7 +116,9 @@ def build_and_load(source):
     if lib is None:
         import torch  # noqa: F401  (same reason as _native.load: bind to torch's HIP runtime)
         lib = C.CDLL(path)
-        lib.mi_ode_plugin_get.restype = C.c_void_p
-        lib.mi_ode_plugin_get.argtypes = [C.c_int]
+        for name in ('mi_ode_plugin_get', 'mi_ode_hyper_plugin_get'):     # (a row-local plugin exports the first, a hyper plugin the second)
+            if hasattr(lib, name):
+                getattr(lib, name).restype = C.c_void_p
+                getattr(lib, name).argtypes = [C.c_int]
         _loaded[path] = lib
     return lib

@@ -1671,6 +1671,8 @@ class _GeneratedRHS(R.DeviceRHS):
         return self._sources[dtype]
 
     _plugin = R.CustomRowLocal._plugin
+    hyper_source = R.CustomRowLocal.hyper_source          # (row-local programs only: the hypersolver kernels take one trajectory per thread)
+    hyper_plugin = R.CustomRowLocal.hyper_plugin
 
     def fill(self, rhs, dtype, device):
         keep = super(_GeneratedRHS, self).fill(rhs, dtype, device)

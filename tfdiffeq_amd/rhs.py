@@ -462,6 +462,30 @@ class CustomRowLocal(DeviceRHS):
     def cache_key(self, dtype, device):
         return super(CustomRowLocal, self).cache_key(dtype, device) + (self._plugin(dtype)[1],)
 
+    def hyper_source(self, dtype):
+        """The hyper plugin of this system (csrc/mi_ode_hyper_plugin.h): the same functor behind the hypersolver kernels."""
+        return hyper_source_of(self.source(dtype))
+
+    def hyper_plugin(self, dtype):
+        """(library, address of the mi_ode_hyper_plugin table) for `dtype`; compiled once, cached by source and header hash."""
+        plugins = self.__dict__.setdefault('_hyper_plugins', {})
+        hit = plugins.get(dtype)
+        if hit is None:
+            from . import _plugin_build
+            lib = _plugin_build.build_and_load(self.hyper_source(dtype))
+            table = lib.mi_ode_hyper_plugin_get(N.dtype_code(dtype))
+            if not table:
+                raise N.NativeError('hyper plugin exports no table for %s' % dtype)
+            hit = (lib, int(table))
+            plugins[dtype] = hit
+        return hit
+
+
+def hyper_source_of(rowlocal_source):
+    """A row-local plugin translation unit (mi_ode_plugin.h) turned into the hyper plugin of the same functor."""
+    src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_hyper_plugin.h"')
+    return src.replace('MI_ODE_DEFINE_ROWLOCAL_PLUGIN(', 'MI_ODE_DEFINE_HYPER_PLUGIN(')
+
 
 _COOP_TEMPLATE = """// generated by tfdiffeq_amd.rhs.CustomCoop - do not edit
 #define {dtype_macro} 1
