@@ -556,6 +556,37 @@ typedef struct mi_ode_hyper {
  * workspace first), or a negative MI_ODE_E_*. */
 int mi_ode_hyper_run(const mi_ode_hyper* desc, void* stream);
 
+/* ---- (E) convolutional ODE function (tfdiffeq/models/conv_odenet.py: Conv2dODEFunc) -----------------------------------------
+ * f(t, y) = conv3(act(conv2(act(conv1(y))))) on NCHW images: conv1 1x1 C -> F, conv2 3x3 zero-padded "same" F -> F, conv3 1x1
+ * F -> C, all with biases; time dependent: every conv sees concat([t, x]) along the channels (time is input channel 0, zero padded
+ * in conv2 like every other channel).  One call = one Runge-Kutta stage: y_s = y0 + sum_j (dt * beta_row[j]) * ks[j] (the operation
+ * order of mi_ode_lincomb_dev; n_k = 0: y_s = y0) and k_out = sign * f(sign * t, y_s), as ONE kernel launch (csrc/mi_ode_conv.h).
+ * Box: 1 <= channels <= MI_ODE_CONV_MAX_C, 1 <= filters <= MI_ODE_CONV_MAX_F, any height / width / batch.  Weights, device, in
+ * the state dtype (Fp = filters rounded up to 16; td = 1 when time dependent, else 0):
+ *   w1  [filters][td + channels]     conv1.weight as torch holds it (column 0: time)
+ *   w2  [9][Fp][Fp]                  conv2.weight[:, td:] as [tap = 3 ky + kx][in][out], zero padded to Fp
+ *   w2t [9][filters]                 conv2.weight[:, 0] as [tap][out] (time dependent only; else nullable)
+ *   w3  [channels][td + filters]     conv3.weight as torch holds it (column 0: time)
+ *   b1, b2 [filters], b3 [channels] */
+#define MI_ODE_CONV_MAX_C 16
+#define MI_ODE_CONV_MAX_F 128
+enum mi_ode_conv_act { MI_ODE_CONV_ACT_RELU = 0, MI_ODE_CONV_ACT_SOFTPLUS = 1, MI_ODE_CONV_ACT_TANH = 2 };   /* softplus: beta 1, threshold 20 */
+typedef struct mi_ode_conv_desc {
+  int32_t dtype;              /* enum mi_ode_dtype */
+  int32_t activation;         /* enum mi_ode_conv_act */
+  int32_t time_dependent;     /* 0 / 1 */
+  int32_t reserved;
+  double sign;                /* +1, or -1 on a reversed time axis: k = -f(-t, y) */
+  int64_t batch;
+  int32_t channels, height, width, filters;
+  const void *w1, *b1, *w2, *w2t, *b2, *w3, *b3;
+} mi_ode_conv_desc;
+/* y0, ks[j], k_out, y_out: device [batch, channels, height, width] contiguous; beta_row: host [n_k] (0 <= n_k <= 14); dt_dev: device
+ * float64 step size (read when the kernel runs; unused when n_k = 0); t_dev: device stage time in the state dtype; y_out: nullable,
+ * receives y_s.  Enqueues one launch on `stream`; returns 0 or a negative MI_ODE_E_*. */
+int mi_ode_conv_stage(const mi_ode_conv_desc* desc, const void* y0, const void* const* ks, int32_t n_k, const double* beta_row,
+                      const double* dt_dev, const void* t_dev, void* k_out, void* y_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

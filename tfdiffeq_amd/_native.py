@@ -120,6 +120,19 @@ class HyperDesc(C.Structure):
                 ('rhs', Rhs), ('layers', HyperLayer * HYPER_MAX_LAYERS)]
 
 
+CONV_MAX_C, CONV_MAX_F = 16, 128
+CONV_ACT_RELU, CONV_ACT_SOFTPLUS, CONV_ACT_TANH = 0, 1, 2
+
+
+class ConvDesc(C.Structure):
+    """mi_ode_conv_desc: one Runge-Kutta stage of the convolutional ODE function in one launch (include/mi_ode.h section E)."""
+    _fields_ = [('dtype', C.c_int32), ('activation', C.c_int32), ('time_dependent', C.c_int32), ('reserved', C.c_int32),
+                ('sign', C.c_double), ('batch', C.c_int64),
+                ('channels', C.c_int32), ('height', C.c_int32), ('width', C.c_int32), ('filters', C.c_int32),
+                ('w1', C.c_void_p), ('b1', C.c_void_p), ('w2', C.c_void_p), ('w2t', C.c_void_p), ('b2', C.c_void_p),
+                ('w3', C.c_void_p), ('b3', C.c_void_p)]
+
+
 class Stats(C.Structure):
     _fields_ = [('n_attempts', C.c_int64), ('n_accepted', C.c_int64), ('n_rejected', C.c_int64), ('nfe', C.c_int64),
                 ('t', C.c_double), ('dt', C.c_double), ('last_ratio', C.c_double),
@@ -212,6 +225,8 @@ _PROTOS = {
     'mi_ode_adams_update_phi': (C.c_int, [C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_double),
                                           C.POINTER(C.c_void_p), C.c_void_p]),
     'mi_ode_hyper_run': (C.c_int, [C.POINTER(HyperDesc), C.c_void_p]),
+    'mi_ode_conv_stage': (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_double), C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mi_ode_interp_eval': (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                      C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double,
                                      C.c_double, C.c_void_p, C.c_void_p]),

@@ -323,6 +323,12 @@ class DeviceControlledRK(object):
         d.safety, d.ifactor, d.dfactor = float(solver.safety), float(solver.ifactor), float(solver.dfactor)
         d.max_num_steps = int(solver.max_num_steps)
         self.S = len(self.tableau.alpha)
+        # a right-hand side with a fused stage kernel (rhs.Conv2dODE, also behind misc._TupleFunc / _ReverseFunc): one launch per stage
+        # forms the stage state and evaluates f; every other callable keeps the lincomb + f path below
+        st = getattr(self.func, 'stage_rhs', None)
+        y = y0[0]
+        self.stage_rhs = st if (st is not None and self.ncomp == 1 and st.supports(y) and not y.requires_grad) else None
+        self._stage_note = '' if self.stage_rhs is None else ', fused stage kernel'
         self._key = (bytes(d), str(self.device))
         self.h = _opq_handle(self.lib, self._key, d, self.device)
         h = self.h
@@ -354,7 +360,14 @@ class DeviceControlledRK(object):
         tb = self.tableau
         k = [[f0_] for f0_ in self.F0]
         yi = None
-        for s, beta_i in enumerate(tb.beta):
+        if self.stage_rhs is not None:                                                               # (py_calls: no Python evaluation)
+            last = len(tb.beta) - 1
+            for s, beta_i in enumerate(tb.beta):
+                k_, y_ = self.stage_rhs.stage(self.ts_views[s], self.Y0[0], k[0], beta_i, self.dt_dev, want_y=self.fsal and s == last)
+                k[0].append(k_)
+                if y_ is not None:
+                    yi = (y_,)
+        for s, beta_i in enumerate(tb.beta if self.stage_rhs is None else ()):
             yi = tuple(_lincomb(y0_, beta_i, k_, self.dt_dev) for y0_, k_ in zip(self.Y0, k))      # rk_common.py:51
             self.py_calls += 1
             for k_, f_ in zip(k, self.func(self.ts_views[s], yi)):                                   # rk_common.py:52
@@ -427,7 +440,8 @@ class DeviceControlledRK(object):
         outs = tuple(torch.empty((T,) + tuple(y.shape), dtype=y.dtype, device=y.device) for y in y0)
         for o, y in zip(outs, y0):
             o[0].copy_(y)
-        self.info = {'engine': 'device-controlled attempts (one Python evaluation per stage)', 'replays': 0, 'polls': 0}
+        self.info = {'engine': 'device-controlled attempts (%s)' % ('fused stage kernel, one launch per stage' if self.stage_rhs is not None
+                                                                   else 'one Python evaluation per stage'), 'replays': 0, 'polls': 0}
         self.py_calls = 0
         if T == 1:
             return outs
@@ -457,7 +471,7 @@ class DeviceControlledRK(object):
             done = False
             autograd = _AutogradSeen()
             if replay_only:
-                self.info['engine'] = 'device-controlled attempts (hipGraph recorded by an earlier call, replayed)'
+                self.info['engine'] = 'device-controlled attempts (hipGraph recorded by an earlier call, replayed%s)' % self._stage_note
                 chunk = 8                                          # (nothing is known about this call's step sizes yet; replays after `done` are no-ops)
                 while not done:
                     for _ in range(chunk):
@@ -479,7 +493,7 @@ class DeviceControlledRK(object):
                     if not self._try_capture():
                         mode = False
                         continue
-                    self.info['engine'] = 'device-controlled attempts (hipGraph replay, %d eager attempts first)' % eager
+                    self.info['engine'] = 'device-controlled attempts (hipGraph replay, %d eager attempts first%s)' % (eager, self._stage_note)
                     while not done:
                         chunk = self._chunk(t_end)
                         for _ in range(chunk):
@@ -488,5 +502,6 @@ class DeviceControlledRK(object):
                         done, rc = self._poll()
                         self.info['polls'] += 1
         self.info['eager_attempts'] = eager
+        self.info['python_evaluations'] = self.py_calls          # (0 on the fused stage path: f ran inside the stage kernels)
         self.info['autograd_in_f'] = autograd.seen
         return outs

@@ -348,6 +348,7 @@ class _TupleFunc(object):
     def __init__(self, base):
         self.base = base
         self.device_rhs = base if getattr(base, 'kind', 0) else None
+        self.stage_rhs = getattr(base, 'stage_rhs', None)          # a descriptor with a fused stage kernel (rhs.Conv2dODE)
         self._mi_no_capture = getattr(base, '_mi_no_capture', False)
 
     def __call__(self, t, y):
@@ -361,6 +362,8 @@ class _ReverseFunc(object):
         self.base = base
         rhs = getattr(base, 'device_rhs', None)
         self.device_rhs = rhs.reversed() if rhs is not None else None
+        st = getattr(base, 'stage_rhs', None)
+        self.stage_rhs = st.reversed() if st is not None else None     # (the sign travels into the stage kernel)
         self.per_component = getattr(base, 'per_component', False)
         self._mi_no_capture = getattr(base, '_mi_no_capture', False)
 

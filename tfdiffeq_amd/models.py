@@ -106,13 +106,12 @@ class ODEBlock(nn.Module):
 
     def __init__(self, odefunc, is_conv=False, tol=1e-3, adjoint=False, solver='dopri5'):
         super(ODEBlock, self).__init__()
-        if is_conv:
-            raise NotImplementedError('convolutional ODE functions are out of scope (SURVEY.md section 2)')
+        self.is_conv = is_conv
         self.adjoint = adjoint
         self.odefunc = odefunc
         self.tol = tol
         self.method = solver
-        self.channel_axis = -1
+        self.channel_axis = 1 if is_conv else -1                 # conv: NCHW images, augmentation along the channels (dim 1)
         if solver == 'dopri5':
             self.options = {'max_num_steps': MAX_NUM_STEPS}      # :126-127
         else:
@@ -125,8 +124,10 @@ class ODEBlock(nn.Module):
         else:
             integration_time = torch.as_tensor(eval_times, dtype=x.dtype)
         if self.odefunc.augment_dim > 0:                         # :154-176 zero augmentation
-            aug = torch.zeros(x.shape[0], self.odefunc.augment_dim, dtype=x.dtype, device=x.device)
-            x_aug = torch.cat([x, aug], dim=-1)
+            shape = list(x.shape)
+            shape[self.channel_axis] = self.odefunc.augment_dim
+            aug = torch.zeros(shape, dtype=x.dtype, device=x.device)
+            x_aug = torch.cat([x, aug], dim=self.channel_axis)
         else:
             x_aug = x
         needs_grad = torch.is_grad_enabled() and (x_aug.requires_grad or any(p.requires_grad for p in self.odefunc.parameters()))
@@ -138,9 +139,17 @@ class ODEBlock(nn.Module):
             out = odeint_adjoint(self.odefunc, x_aug, integration_time, **kw)
         else:
             fused = None if needs_grad else self.odefunc.device_rhs()
-            # (the tile kernels, or - float64 / wider networks, round 5 - the cooperative one-launch kernel; if neither takes the problem
-            # the solver runs the descriptor's own forward() as a callable on the device-controlled engine and says so once)
-            func = fused if (fused is not None and (fused.supports(x_aug) or fused.supports_coop(x_aug))) else self.odefunc
+            if self.is_conv:
+                # rhs.Conv2dODE: the fused stage kernel where it takes the shape and is the faster route (larger shapes run the torch
+                # module, rhs.Conv2dODE.FUSED_MAX_CONV2_FLOP); outside its box the descriptor says why, once
+                why = fused.in_box(x_aug) if x_aug.is_cuda else 'a host tensor'
+                if why and x_aug.is_cuda:
+                    fused.warn_limits(x_aug, why)
+                func = fused if (not why and fused.faster_than_torch(x_aug)) else self.odefunc
+            else:
+                # (the tile kernels, or - float64 / wider networks, round 5 - the cooperative one-launch kernel; if neither takes the problem
+                # the solver runs the descriptor's own forward() as a callable on the device-controlled engine and says so once)
+                func = fused if (fused is not None and (fused.supports(x_aug) or fused.supports_coop(x_aug))) else self.odefunc
             with torch.no_grad():
                 out = odeint(func, x_aug, integration_time, **kw)                           # :184-186
             if func is fused:                                    # f ran inside the kernel: the counter the reference exposes
@@ -152,6 +161,9 @@ class ODEBlock(nn.Module):
     def trajectory(self, x, timesteps):
         """dense_odenet.py:193-205."""
         return self.forward(x, eval_times=torch.linspace(0., 1., timesteps))
+
+
+from .conv_models import Conv2dODEFunc, Conv2dODENet, Conv2dTime  # noqa: E402,F401  (conv_odenet.py's classes, re-exported)
 
 
 class ODENet(nn.Module):

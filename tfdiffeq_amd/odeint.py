@@ -134,6 +134,11 @@ _LOWER_METHODS = ('dopri5', 'tsit5', 'bosh3', 'dopri8', 'adaptive_heun', 'euler'
                   'fixed_adams', 'adams')
 
 
+def _descriptor(func):
+    """A DeviceRHS: a catalogue descriptor (`kind`) or one with a fused stage of its own (rhs.Conv2dODE, kind 0) - never traced."""
+    return bool(getattr(func, 'kind', 0)) or getattr(func, 'stage_rhs', None) is not None
+
+
 def _try_lower(func, y0, method, options):
     """(Lowered, None) / (None, reason) when this call is one the tracer is asked to look at, None when it is not (a DeviceRHS, a CPU
     state - the solver raises its own error -, a tuple of several components, an explicit request for one of the callable engines).
@@ -142,7 +147,7 @@ def _try_lower(func, y0, method, options):
     import torch
     opts = options or {}
     mode = opts.get('lower', LOWER_DEFAULT)
-    if mode is False or mode == 'off' or not callable(func) or getattr(func, 'kind', 0) or getattr(func, 'per_component', False):
+    if mode is False or mode == 'off' or not callable(func) or _descriptor(func) or getattr(func, 'per_component', False):
         return None
     if method is not None and method not in _LOWER_METHODS:
         return None
@@ -384,7 +389,7 @@ def _wants_grad(func, y0):
         return True
     if isinstance(func, torch.nn.Module):
         return any(p.requires_grad for p in func.parameters())
-    if getattr(func, 'kind', 0) or not callable(func):     # a DeviceRHS descriptor: weights are plain device tensors
+    if _descriptor(func) or not callable(func):     # a DeviceRHS descriptor: weights are plain device tensors
         return False
     # a plain callable over trainable state (`lambda t, y: net(y)`): the reference's tape would reach net's parameters.  Whether THIS
     # callable does is a property of its autograd graph (one cached probe evaluation), not of what its closure could name.
@@ -393,7 +398,7 @@ def _wants_grad(func, y0):
 
 def _plain_callable_no_grad_state(func, y0):
     import torch
-    if not torch.is_grad_enabled() or not callable(func) or getattr(func, 'kind', 0) or isinstance(func, torch.nn.Module):
+    if not torch.is_grad_enabled() or not callable(func) or _descriptor(func) or isinstance(func, torch.nn.Module):
         return False
     ys = y0 if isinstance(y0, (tuple, list)) else (y0,)
     return all(isinstance(y, torch.Tensor) and not y.requires_grad for y in ys)

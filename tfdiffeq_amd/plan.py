@@ -47,6 +47,31 @@ def _callable_engine(method, options, why):
             'launches': 'several per stage, the controller on the host', 'why': why}
 
 
+def plan_conv(rhs, y, method, options=None):
+    """rhs.Conv2dODE: the fused stage kernel (csrc/mi_ode_conv.h) inside its box, the torch module on the callable engine outside."""
+    why = rhs.in_box(y)
+    base = {'family': 'conv2d', 'box': 'NCHW float32 / float64, C <= %d, F <= %d, relu / softplus / tanh, any H, W, batch' % (rhs.MAX_C, rhs.MAX_F)}
+    if why:
+        d = _callable_engine(method, options, 'rhs.Conv2dODE outside the fused kernel\'s box (%s): the torch module runs' % why)
+    elif method in ADAPTIVE:
+        d = _callable_engine(method, options, 'rhs.Conv2dODE: each Runge-Kutta stage (stage state + three convolutions) is one launch')
+        if d['engine'] == 'callable':                    # (graph='host', force_plane_kernels, process_group: the host loop calls f per stage)
+            d['kernel'] = 'k_conv_stage<%s> per stage + k_opq_norms + k_opq_commit (graph_step.DeviceControlledRK)' % _tname(y.dtype)
+        else:
+            d['kernel'] = 'k_conv_stage<%s> per evaluation of f, plane kernels between' % _tname(y.dtype)
+            d['why'] = 'rhs.Conv2dODE on the host-controlled loop (the options ask for it): one fused evaluation per stage'
+    else:
+        d = {'engine': 'plane kernels', 'kernel': 'k_conv_stage<%s> per evaluation of f, plane kernels between' % _tname(y.dtype),
+             'launches': 'one per evaluation of f plus the solver\'s state arithmetic', 'why': 'rhs.Conv2dODE on a fixed-grid / multistep method'}
+    d.update(base)
+    d['fused_stage'] = not why
+    if not why:
+        d['odeblock'] = ('fused stage kernel' if rhs.faster_than_torch(y) else
+                         'torch module: %.3g GFLOP of conv2 per evaluation > %.3g, where the fused kernel measured slower than torch'
+                         % (rhs.conv2_flop(y) / 1e9, rhs.FUSED_MAX_CONV2_FLOP / 1e9))
+    return d
+
+
 def plan_rhs(rhs, y, method, options=None):
     """The decision for a DeviceRHS and ONE state tensor (shape / dtype are read, nothing else)."""
     opts = options or {}
@@ -141,6 +166,10 @@ def plan(func, y0, t=None, rtol=1e-7, atol=1e-9, method=None, options=None):
         raise KeyError(method)
     ys = y0 if isinstance(y0, (tuple, list)) else (y0,)
     lower_info = None
+    if getattr(func, 'stage_rhs', None) is not None and len(ys) == 1:
+        d = plan_conv(func.stage_rhs, ys[0], method, opts)
+        d['lower'] = None
+        return d
     rhs = func if getattr(func, 'kind', 0) else None
     if rhs is None and getattr(func, 'per_component', False):
         base = func.device_rhs

@@ -588,3 +588,166 @@ class CustomCoop(DeviceRHS):
     def cache_key(self, dtype, device):
         return super(CustomCoop, self).cache_key(dtype, device) + (self._plugin(dtype)[1],)
 
+
+
+# ---------------------------------------------------------------------------------------------
+# convolutional ODE function (tfdiffeq/models/conv_odenet.py: Conv2dODEFunc)
+# ---------------------------------------------------------------------------------------------
+class Conv2dODE(DeviceRHS):
+    """f(t, y) = conv3(act(conv2(act(conv1(y))))) on NCHW images [batch, C, H, W]: conv1 1x1 C -> F, conv2 3x3 zero-padded "same"
+    F -> F, conv3 1x1 F -> C, all with biases; time dependent: every conv sees concat([t, x]) along the channels (time = channel 0).
+    The weights are torch's nn.Conv2d ones ([out, in, kh, kw]); the descriptor keeps its own copies - the kernel's packed layouts
+    (include/mi_ode.h section E) and the originals for `forward` - which `refresh()` rewrites IN PLACE.
+
+    Not a `mi_ode_rhs_kind` (kind 0): the whole-call kernels do not take it.  It runs on the callable engines, where
+      * `__call__(t, y)` on a CUDA tensor outside autograd is ONE launch of the fused kernel (csrc/mi_ode_conv.h) on the current stream,
+      * `stage(...)` - the device-controlled adaptive engine's hook (graph_step.DeviceControlledRK) - forms the Runge-Kutta stage state
+        y0 + sum (dt beta_j) k_j inside the same launch.
+    Box: float32 / float64, C <= 16, F <= 128, relu / softplus / tanh, any H, W and batch; outside it (or under autograd) `forward`,
+    the torch definition, runs - said once."""
+    ACTIVATIONS = {'relu': N.CONV_ACT_RELU, 'softplus': N.CONV_ACT_SOFTPLUS, 'tanh': N.CONV_ACT_TANH}
+    MAX_C, MAX_F = N.CONV_MAX_C, N.CONV_MAX_F
+    fixed_grid_fused = False
+    multistep_fused = False
+    _told_limits = set()
+
+    def __init__(self, w1, b1, w2, b2, w3, b3, activation='relu', time_dependent=False):
+        super(Conv2dODE, self).__init__()
+        self.activation = str(activation)
+        self.time_dependent = bool(time_dependent)
+        td = 1 if self.time_dependent else 0
+        self.F = int(w1.shape[0])
+        self.C = int(w3.shape[0])
+        self.Fp = (self.F + 15) // 16 * 16
+        if tuple(w1.shape) != (self.F, self.C + td, 1, 1) or tuple(w2.shape) != (self.F, self.F + td, 3, 3) or \
+                tuple(w3.shape) != (self.C, self.F + td, 1, 1):
+            raise ValueError('Conv2dODE: expected conv weights [F, C%s, 1, 1], [F, F%s, 3, 3], [C, F%s, 1, 1]; got %s, %s, %s'
+                             % (('+1',) * 3 if td else ('',) * 3) + (tuple(w1.shape), tuple(w2.shape), tuple(w3.shape)))
+        kw = dict(dtype=w1.dtype, device=w1.device)
+        self.Ws = [torch.empty_like(w, memory_format=torch.contiguous_format) for w in (w1, w2, w3)]      # torch layout (forward)
+        self.bs = [torch.empty_like(b) for b in (b1, b2, b3)]
+        self.w2p = torch.zeros(9, self.Fp, self.Fp, **kw)                                               # [tap][in][out], zero padded
+        self.w2t = torch.zeros(9, self.F, **kw)                                                         # [tap][out]: the time channel
+        self.refresh(w1, b1, w2, b2, w3, b3)
+
+    def refresh(self, w1, b1, w2, b2, w3, b3):
+        """Copy the live parameters into this descriptor's buffers (same storage: nothing cached on them goes stale)."""
+        td = 1 if self.time_dependent else 0
+        with torch.no_grad():
+            for dst, src in zip(self.Ws + self.bs, (w1, w2, w3, b1, b2, b3)):
+                dst.copy_(src)
+            self.w2p[:, :self.F, :self.F].copy_(w2[:, td:].permute(2, 3, 1, 0).reshape(9, self.F, self.F))
+            if td:
+                self.w2t.copy_(w2[:, 0].permute(1, 2, 0).reshape(9, self.F))
+        return self
+
+    @property
+    def stage_rhs(self):
+        return self
+
+    # -- torch definition ------------------------------------------------------------------------
+    def forward(self, t, y):
+        F_ = torch.nn.functional
+        act = {'relu': torch.relu, 'softplus': F_.softplus, 'tanh': torch.tanh}.get(self.activation)
+        if act is None:
+            act = getattr(F_, self.activation, None) or getattr(torch.nn, self.activation)()
+        W = [self._dev(w, y.dtype, y.device) for w in self.Ws]
+        b = [self._dev(v, y.dtype, y.device) for v in self.bs]
+
+        def conv(i, x, pad):
+            if self.time_dependent:
+                tt = torch.ones_like(x[:, :1]) * torch.as_tensor(t, dtype=y.dtype, device=y.device)
+                x = torch.cat([tt, x], dim=1)
+            return F_.conv2d(x, W[i], b[i], padding=pad)
+        return conv(2, act(conv(1, act(conv(0, y, 0)), 1)), 0)
+
+    # -- the fused kernel ----------------------------------------------------------------------------
+    def in_box(self, y):
+        """'' when the fused kernel takes this state, else the reason it does not."""
+        if not isinstance(y, torch.Tensor) or y.dim() != 4 or y.shape[1] != self.C:
+            return 'the state is not [batch, %d, H, W]' % self.C
+        if y.dtype not in (torch.float32, torch.float64):
+            return 'dtype %s' % str(y.dtype).replace('torch.', '')
+        if self.activation not in self.ACTIVATIONS:
+            return 'activation %r (the kernel has %s)' % (self.activation, sorted(self.ACTIVATIONS))
+        if self.C > self.MAX_C:
+            return 'C + augment_dim = %d > %d' % (self.C, self.MAX_C)
+        if self.F > self.MAX_F:
+            return 'num_filters = %d > %d' % (self.F, self.MAX_F)
+        if y.numel() == 0:
+            return 'an empty state'
+        return ''
+
+    def supports(self, y):
+        return isinstance(y, torch.Tensor) and y.is_cuda and not self.in_box(y)
+
+    # Measured on the MI355X (profiles/r08_conv_bench.txt, float32 dopri5 calls): the fused path wins where the call is launch-bound
+    # (10 x 3 x 5 x 5, F = 10: 2.8 x) and loses where conv2 dominates (the full-batch MNIST / CIFAR shapes, 7 - 30 GFLOP of conv2 per
+    # evaluation: 0.47 - 0.68 x torch's speed; the kernel reaches ~21 % of the matrix peak there, MIOpen more).  The batch sweep at
+    # 6 x 28 x 28, F = 64 puts the crossover between B = 32 (1.85 GFLOP, 1.15 x) and B = 64 (3.7 GFLOP, 0.98 x); `ODEBlock` and `plan()`
+    # route shapes above 2.5 GFLOP of conv2 per evaluation to torch (measured at that one F; other widths may cross elsewhere).
+    FUSED_MAX_CONV2_FLOP = 2.5e9
+
+    def conv2_flop(self, y):
+        return 2.0 * y.shape[0] * y.shape[2] * y.shape[3] * 9 * self.F * self.F
+
+    def faster_than_torch(self, y):
+        return self.conv2_flop(y) <= self.FUSED_MAX_CONV2_FLOP
+
+    def warn_limits(self, y, why):
+        key = (str(y.dtype), self.C, self.F, self.activation, why)
+        if key not in Conv2dODE._told_limits:
+            Conv2dODE._told_limits.add(key)
+            import warnings
+            warnings.warn('tfdiffeq_amd.rhs.Conv2dODE: the fused stage kernel takes float32 / float64 NCHW states with C <= %d, F <= %d and '
+                          'relu / softplus / tanh; this problem (%s) runs the torch module instead' % (self.MAX_C, self.MAX_F, why))
+
+    def __call__(self, t, y):
+        if not isinstance(y, torch.Tensor) or not y.is_cuda:
+            N.require_gpu_tensor(y, 'the state of rhs.Conv2dODE')
+        why = self.in_box(y)
+        if why:
+            self.warn_limits(y, why)
+        if why or (torch.is_grad_enabled() and y.requires_grad):
+            return super(Conv2dODE, self).__call__(t, y)
+        self.nfe += 1
+        return self.stage(t, y)[0]
+
+    def _t_dev(self, t, like):
+        if isinstance(t, torch.Tensor) and t.is_cuda and t.numel() == 1:
+            return t if t.dtype == like.dtype and t.device == like.device else t.to(device=like.device, dtype=like.dtype)
+        return torch.full((), float(t), dtype=like.dtype, device=like.device)
+
+    def stage(self, t, y0, ks=(), beta=(), dt=None, want_y=False):
+        """(k, y_s or None): k = f(t, y_s) with y_s = y0 + sum_j (dt * beta[j]) * ks[j] (mi_ode_lincomb_dev's arithmetic), one launch on
+        the current stream.  dt: a 0-d float64 device tensor or a misc._DevScalar (read when the kernel runs); t: the stage time."""
+        import ctypes as C
+        from .misc import _DevScalar
+        N.require_gpu_tensor(y0, 'the state of rhs.Conv2dODE')
+        y0 = y0 if y0.is_contiguous() else y0.contiguous()
+        dtype, dev = y0.dtype, y0.device
+        d = N.ConvDesc()
+        d.dtype = N.dtype_code(dtype)
+        d.activation = self.ACTIVATIONS[self.activation]
+        d.time_dependent = 1 if self.time_dependent else 0
+        d.sign = float(self.sign)
+        d.batch, d.channels, d.height, d.width, d.filters = int(y0.shape[0]), self.C, int(y0.shape[2]), int(y0.shape[3]), self.F
+        w1, w2, w3 = (self._dev(w, dtype, dev) for w in (self.Ws[0], self.w2p, self.Ws[2]))
+        b1, b2, b3 = (self._dev(v, dtype, dev) for v in self.bs)
+        w2t = self._dev(self.w2t, dtype, dev)
+        d.w1, d.b1, d.w2, d.w2t, d.b2, d.w3, d.b3 = (x.data_ptr() for x in (w1, b1, w2, w2t, b2, w3, b3))
+        tt = self._t_dev(t, y0)
+        ks = [k if k.is_contiguous() else k.contiguous() for k in ks]
+        nk = len(ks)
+        kp = (C.c_void_p * max(nk, 1))(*[k.data_ptr() for k in ks])
+        bp = (C.c_double * max(nk, 1))(*[float(c) for c in beta])
+        dtp = 0
+        if nk:
+            dtp = dt.ptr if isinstance(dt, _DevScalar) else dt.data_ptr()
+        k_out = torch.empty_like(y0)
+        y_out = torch.empty_like(y0) if want_y else None
+        lib = N.load()
+        N.check(lib.mi_ode_conv_stage(C.byref(d), C.c_void_p(y0.data_ptr()), kp, nk, bp, C.c_void_p(dtp), C.c_void_p(tt.data_ptr()),
+                                      C.c_void_p(k_out.data_ptr()), C.c_void_p(y_out.data_ptr() if want_y else 0),
+                                      N.stream_ptr(dev)), 'mi_ode_conv_stage')
+        return k_out, y_out
