@@ -228,7 +228,7 @@ def test_adjoint_parameter_order_round_trip():
 
 def test_fused_paths_are_not_chosen_for_host_tensors_or_uncovered_functions():
     import torch
-    from tfdiffeq_amd import adjoint, models, rhs, solvers
+    from tfdiffeq_amd import adjoint, models, rhs
     f = models.ODEFunc(3, 5, non_linearity='tanh')
     cfg = dict(adjoint_method=None, adjoint_options=None, adjoint_rtol=1e-6, adjoint_atol=1e-9)
     wrapped = adjoint._TupleModule(f)
@@ -248,11 +248,16 @@ def test_fused_paths_are_not_chosen_for_host_tensors_or_uncovered_functions():
     assert models.ODEFunc(3, 5).device_rhs().activation == 'relu'
     # tuple lift: only row-local systems, 2..8 components, device tensors
     lift = rhs.PerComponent(rhs.Lorenz())
-    assert solvers._fusable_tuple(lift, (torch.zeros(4, 3), torch.zeros(2, 3))) is None          # host tensors
-    assert solvers._fusable_tuple(rhs.Lorenz(), (torch.zeros(4, 3), torch.zeros(2, 3))) is None  # not lifted
-    dense = rhs.PerComponent(rhs.Linear.from_matrix(torch.eye(4)))                               # not row-local: a plain callable
-    assert solvers._fusable_tuple(dense, (torch.zeros(4, 4), torch.zeros(2, 4))) is None
     import pytest
+    from tfdiffeq_amd import _native as N
+    from tfdiffeq_amd.dopri5 import Dopri5Solver
+    host = (torch.zeros(4, 3), torch.zeros(2, 3))
+    with pytest.raises(N.NativeError):                                                           # host tensors: refused before any routing
+        Dopri5Solver(lift, host, rtol=1e-6, atol=1e-9).integrate(torch.tensor([0., 1.]))
+    assert Dopri5Solver(lift, host, rtol=1e-6, atol=1e-9).route().kind == 'fused_tuple'          # (the route itself does not read the device)
+    assert Dopri5Solver(rhs.Lorenz(), host, rtol=1e-6, atol=1e-9).route().kind != 'fused_tuple'  # not lifted
+    dense = rhs.PerComponent(rhs.Linear.from_matrix(torch.eye(4)))                               # not row-local: a plain callable
+    assert Dopri5Solver(dense, (torch.zeros(4, 4), torch.zeros(2, 4)), rtol=1e-6, atol=1e-9).route().kind != 'fused_tuple'
     with pytest.raises(TypeError):
         rhs.PerComponent(lambda t, y: y)                                                         # not a DeviceRHS
 
@@ -552,3 +557,56 @@ def test_plan_names_the_engine_of_the_five_baseline_configurations():
     assert p['engine'] == 'fused' and p['lower']['kind'] == 'coop'
     p = odeint.plan(rhs.Lorenz(), torch.ones(8, 3, dtype=f64), method='adams')
     assert p['kernel'].startswith('k_adams_vc_rowlocal<double')
+
+
+def _route_net():
+    torch.manual_seed(0)
+    return rhs.from_sequential(torch.nn.Sequential(torch.nn.Linear(64, 128), torch.nn.Tanh(), torch.nn.Linear(128, 128), torch.nn.Tanh(),
+                                                   torch.nn.Linear(128, 64)))
+
+
+# (name, right-hand side, component shapes, dtype, method, options, the route the SOLVER takes).  The first six are calls for which
+# `odeint.plan` used to promise an engine the solver does not take; the last five are the same calls on their fused routes.
+ROUTE_CASES = [
+    ('mlp adaptive_heun', _route_net, [(64, 64)], torch.float32, 'adaptive_heun', None, 'fused_coop'),
+    ('tuple dopri5 force_plane_kernels', lambda: rhs.PerComponent(rhs.Lorenz()), [(8, 3), (4, 3)], torch.float64, 'dopri5', {'force_plane_kernels': True}, 'planes'),
+    ('tuple dopri5 fusion=stage', lambda: rhs.PerComponent(rhs.Lorenz()), [(8, 3), (4, 3)], torch.float64, 'dopri5', {'fusion': 'stage'}, 'callable'),
+    ('tuple rk4 step_size', lambda: rhs.PerComponent(rhs.Lorenz()), [(8, 3), (4, 3)], torch.float64, 'rk4', {'step_size': 0.01}, 'planes'),
+    ('lorenz explicit_adams fusion=stage', rhs.Lorenz, [(8, 3)], torch.float64, 'explicit_adams', {'fusion': 'stage'}, 'planes'),
+    ('lorenz rk4 fusion=stage step_size', rhs.Lorenz, [(8, 3)], torch.float64, 'rk4', {'fusion': 'stage', 'step_size': 0.01}, 'planes'),
+    ('mlp dopri5', _route_net, [(64, 64)], torch.float32, 'dopri5', None, 'fused'),
+    ('tuple dopri5', lambda: rhs.PerComponent(rhs.Lorenz()), [(8, 3), (4, 3)], torch.float64, 'dopri5', None, 'fused_tuple'),
+    ('tuple rk4', lambda: rhs.PerComponent(rhs.Lorenz()), [(8, 3), (4, 3)], torch.float64, 'rk4', None, 'fused_tuple'),
+    ('lorenz explicit_adams', rhs.Lorenz, [(8, 3)], torch.float64, 'explicit_adams', None, 'fused_multistep'),
+    ('lorenz rk4', rhs.Lorenz, [(8, 3)], torch.float64, 'rk4', None, 'fused'),
+]
+PLAN_ENGINE = {'fused': 'fused', 'fused_coop': 'fused', 'fused_tuple': 'fused', 'fused_multistep': 'fused', 'callable': 'callable', 'planes': 'plane kernels'}
+
+
+def route_state(shapes, dtype, device='cpu'):
+    """The state of a ROUTE_CASES row: one tensor, or a tuple of components."""
+    g = torch.Generator().manual_seed(1)
+    ys = tuple((1.0 + 0.1 * torch.randn(*s, generator=g, dtype=torch.float64)).to(dtype).to(device) for s in shapes)
+    return ys[0] if len(ys) == 1 else ys
+
+
+@pytest.mark.parametrize('name,make,shapes,dtype,method,options,kind', ROUTE_CASES, ids=[c[0] for c in ROUTE_CASES])
+def test_solver_route_and_plan_agree(name, make, shapes, dtype, method, options, kind):
+    """The route the solver takes - asked of the solver `odeint` constructs, without integrating - equals the expectation written out
+    above, and `odeint.plan` names the same engine.  No GPU: the state's device is not a routing input."""
+    from tfdiffeq_amd.odeint import SOLVERS
+    f, y0 = make(), route_state(shapes, dtype)
+    _, func, ys, _ = misc._check_inputs(f, y0, torch.tensor([0., 0.05]))
+    solver = SOLVERS[method](func, ys, rtol=1e-6, atol=1e-9, **(options or {}))
+    assert solver.route().kind == kind
+    p = odeint.plan(f, y0, torch.tensor([0., 0.05]), rtol=1e-6, atol=1e-9, method=method, options=options)
+    assert p['engine'] == PLAN_ENGINE[kind], p
+
+
+def test_plan_lowers_a_one_component_tuple_like_odeint():
+    """`odeint` lowers the tensor form of a one-component tuple state and re-enters with a tensor (odeint.py `_try_lower`): `plan` says so."""
+    A = torch.eye(8, dtype=torch.float64)
+    y = torch.ones(4, 8, dtype=torch.float64)
+    p1 = odeint.plan(lambda t, ys: (ys[0] @ A,), (y,), method='dopri5', options={'lower': 'auto'})
+    p = odeint.plan(lambda t, y_: y_ @ A, y, method='dopri5', options={'lower': 'auto'})
+    assert p1['engine'] == 'fused' and p1['lower']['lowered'] and p1['kernel'] == p['kernel']

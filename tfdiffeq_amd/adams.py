@@ -17,9 +17,10 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .misc import (_contig, _convert_to_tensor, _handle_unused_kwargs, _is_iterable, _np_dtype, _optimal_step_size, _reduce_workspace,
+from . import dispatch as D
+from .misc import (_assert_increasing, _contig, _convert_to_tensor, _handle_unused_kwargs, _is_iterable, _np_dtype, _optimal_step_size, _reduce_workspace,
                    _scalar_tensor, _select_initial_step)
-from .solvers import AdaptiveStepsizeODESolver
+from .solvers import _EULER_SHAPE, AdaptiveStepsizeODESolver, _FusedEngine, _one_launch
 
 _MIN_ORDER = 1
 _MAX_ORDER = 12
@@ -71,37 +72,33 @@ class VariableCoefficientAdamsBashforth(AdaptiveStepsizeODESolver):
         like = self.y0[0]
         return self.func(_scalar_tensor(_np_dtype(like.dtype).type(t), like), y)
 
+    def route(self):
+        """The engine this call is routed to (dispatch.Route), decided without running anything."""
+        return D.multistep(self.func, self.y0, "options['force_plane_kernels']" if self._force_planes else '')
+
     def integrate(self, t):
         """A row-local catalogue system with a single state tensor: the whole call - the deque of backward differences, g / beta,
         the error ratios, the order selection - is ONE kernel launch (csrc/mi_ode_adams_vc.h).  Everything else: the per-step loop of
         the base class over plane kernels."""
-        from .solvers import _EULER_SHAPE, _FusedEngine, _cached_engine_or_none, _fusable, SyncTimeout
-        from .misc import _assert_increasing
-        rhs = _fusable(self.func, self.y0, multistep=True) if not self._force_planes else None
-        if rhs is not None and getattr(rhs, 'multistep_fused', False) and len(self.y0) == 1:
-            _assert_increasing(t)
-            y = self.y0[0]
-            key = ('adams_vc', rhs.cache_key(y.dtype, y.device), tuple(y.shape), y.dtype, str(y.device), self.max_order,
-                   float(self.rtol[0]), float(self.atol[0]), float(self.safety), float(self.ifactor), float(self.dfactor))
-            # (None: a batch whose workgroups cannot be co-resident - remembered under the key - the per-step loop)
-            eng = _cached_engine_or_none(key, lambda: _FusedEngine(rhs, y, True, _EULER_SHAPE, rtol=self.rtol[0], atol=self.atol[0],
-                                                                   safety=float(self.safety), ifactor=float(self.ifactor),
-                                                                   dfactor=float(self.dfactor), multistep=(3, self.max_order, gamma_star)))
-            out = None
-            if eng is not None:
-                try:
-                    out = eng.integrate(t.to(torch.float64).numpy(), y)
-                except SyncTimeout:                   # hand-off timed out (shared GPU): nothing was committed, take the per-step loop
-                    out = None
-            if out is not None:
-                self.stats = eng.stats.as_dict()
-                self.stats['engine'] = 'fused variable-order Adams kernel (one launch)'
-                return (out,)
-        return super(VariableCoefficientAdamsBashforth, self).integrate(t)
-
-    def before_integrate(self, t):
+        _assert_increasing(t)
         for y_ in self.y0:
             N.require_gpu_tensor(y_, 'y0')
+        route = self.route()
+        self.stats['route'] = route.kind
+        if route.kind == 'fused_multistep':
+            rhs, y = route.rhs, self.y0[0]
+            key = ('adams_vc', rhs.cache_key(y.dtype, y.device), tuple(y.shape), y.dtype, str(y.device), self.max_order,
+                   float(self.rtol[0]), float(self.atol[0]), float(self.safety), float(self.ifactor), float(self.dfactor))
+            eng, out = _one_launch(key, lambda: _FusedEngine(rhs, y, True, _EULER_SHAPE, rtol=self.rtol[0], atol=self.atol[0],
+                                                             safety=float(self.safety), ifactor=float(self.ifactor),
+                                                             dfactor=float(self.dfactor), multistep=(3, self.max_order, gamma_star)),
+                                   lambda eng: eng.integrate(t.to(torch.float64).numpy(), y))
+            if eng is not None:
+                self.stats = dict(eng.stats.as_dict(), engine='fused variable-order Adams kernel (one launch)', route=route.kind)
+                return (out,)
+        return super(VariableCoefficientAdamsBashforth, self).integrate(t)      # the route itself, or dispatch.after(route)
+
+    def before_integrate(self, t):
         prev_f = collections.deque(maxlen=self.max_order + 1)
         prev_t = collections.deque(maxlen=self.max_order + 1)
         phi = collections.deque(maxlen=self.max_order)

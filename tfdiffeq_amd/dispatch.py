@@ -1,0 +1,162 @@
+"""Which engine an `odeint` call runs on: the one decision the solvers (solvers.py, adams.py), `odeint.plan`, `odeint`'s tracer gate and
+`models.ODEBlock` share.  Pure functions of the descriptor behind `func` (`device_rhs`, `per_component`), the state's shapes and dtypes, the
+tableau's shape or the multistep kind, and the normalised options: no engine, no library, no device (the solvers refuse host tensors BEFORE
+they ask).  What only `mi_ode_create` or a run can know - co-residency, a grid hand-off that timed out - is the solvers' fallback to `after`."""
+import collections
+
+import torch
+
+from . import _native as N
+from . import rhs as R
+
+# options['fusion']: the schedule of the fused engine, by name or by the code include/mi_ode.h gives it; normalised where the option is popped
+FUSION = {'auto': 0, 'stage': 1, 'step': 2, 'step_split': 3, 'whole': 4}
+AUTO, STAGE, STEP, WHOLE = (FUSION[k] for k in ('auto', 'stage', 'step', 'whole'))
+
+# kind:  fused            one state tensor on the catalogue / tile / row-local kernels
+#        fused_coop       the cooperative whole-call kernel (a network outside the tile kernels' box, or a tableau they are not instantiated for)
+#        fused_tuple      rhs.PerComponent over one segmented (adaptive) or concatenated (fixed grid) buffer
+#        fused_multistep  the one-launch fixed-order / variable-order Adams kernels
+#        callable         graph_step.DeviceControlledRK: f as a callable, the controller on the device
+#        planes           the host loop over plane kernels
+# rhs: the DeviceRHS a fused engine is built from.  why: the predicate that decided.  told: a descriptor whose family has no kernel for
+# this problem and says so once (`warn_limits`).
+Route = collections.namedtuple('Route', 'kind rhs why told', defaults=(None,))
+
+_TUPLE_WHY = 'rhs.PerComponent of a row-local right-hand side: tuple components share one buffer'
+_PYTHON = {True: 'a Python callable', False: 'a tuple state of a Python callable'}        # by len(y0) == 1
+
+
+def after(route, device_controlled=False):
+    """The order, stated once: fused* -> callable (an adaptive Runge-Kutta call `device_controlled(...)` takes) -> planes."""
+    kind = 'callable' if device_controlled and route.kind.startswith('fused') else 'planes'
+    return Route(kind, None, 'no one-launch kernel for this batch: its workgroups are not co-resident, or the grid hand-off timed out')
+
+
+def _single(rhs, y0, multistep=False):
+    """`rhs` if its fused kernels (multistep: the one-launch Adams kernels, with limits of their own) take the ONE state tensor, else None."""
+    y = y0[0]
+    if rhs is None or len(y0) != 1 or not (isinstance(y, torch.Tensor) and y.dim() >= 1 and y.numel() > 0):
+        return None
+    return rhs if (rhs.supports_multistep if multistep else rhs.supports)(y) else None
+
+
+def _coop(rhs, y0, any_box=False):
+    """`rhs` if the cooperative one-launch kernel is its route for the ONE state tensor (rhs.MLP.supports_coop), else None."""
+    if rhs is None or len(y0) != 1 or not hasattr(rhs, 'supports_coop') or not isinstance(y0[0], torch.Tensor) or y0[0].numel() == 0:
+        return None
+    return rhs if rhs.supports_coop(y0[0], any_box=any_box) else None
+
+
+def _tuple(func, y0):
+    """The row-local DeviceRHS behind a `rhs.PerComponent` lift if this tuple state can travel as one buffer, else None."""
+    rhs, y = getattr(func, 'device_rhs', None), y0[0]
+    if rhs is None or not getattr(func, 'per_component', False) or not getattr(rhs, 'row_local', False) or not 2 <= len(y0) <= N.MAX_SEGMENTS:
+        return None
+    ok = all(isinstance(c, torch.Tensor) and c.dim() >= 1 and c.numel() > 0 and c.dtype == y.dtype and c.device == y.device and rhs.supports(c) for c in y0)
+    return rhs if ok else None
+
+
+def family(rhs):
+    """The kernel family of a descriptor, as csrc `pick_family` sees it: 'rowlocal', 'coop', 'mlp', 'cubic_linear', 'linear' or its class name."""
+    if getattr(rhs, 'row_local', False):
+        return 'rowlocal'
+    if getattr(rhs, 'coop', False) or isinstance(rhs, R.CustomCoop):
+        return 'coop'
+    for cls, name in ((R.MLP, 'mlp'), (R.CubicLinear, 'cubic_linear'), (R.Linear, 'linear')):
+        if isinstance(rhs, cls):
+            return name
+    return type(rhs).__name__
+
+
+def has_kernel(rhs, y):
+    """True when a Runge-Kutta kernel of the descriptor's family takes this state tensor: its own box or the cooperative kernel's."""
+    return _single(rhs, (y,)) is not None or _coop(rhs, (y,)) is not None
+
+
+def device_controlled(y0, rows, *, quartic, force_planes, group, graph):
+    """True where graph_step.DeviceControlledRK takes a callable; False: the loop with the controller on the host."""
+    like = y0[0]
+    if graph == 'host' or force_planes or group or not 1 <= len(y0) <= N.MAX_SEGMENTS or rows + 1 not in (2, 4, 7, 14):
+        return False
+    if like.dtype not in (torch.float32, torch.float64) or any(y.dtype != like.dtype or y.device != like.device or y.numel() == 0 for y in y0):
+        return False
+    return quartic or rows == 6
+
+
+def adaptive_rk(func, y0, rows, fsal, *, quartic=True, force_planes=False, group=False, fusion=AUTO, graph='auto'):
+    """The adaptive Runge-Kutta solvers.  rows, fsal: the tableau's shape; quartic: the dense output is the quartic through the midpoint."""
+    def host(why, told=None):
+        ok = device_controlled(y0, rows, quartic=quartic, force_planes=force_planes, group=group, graph=graph)
+        return Route('callable' if ok else 'planes', None, why, told)
+    dev = getattr(func, 'device_rhs', None)
+    if dev is None:
+        return host(_PYTHON[len(y0) == 1])
+    if force_planes:
+        return host("options['force_plane_kernels']")
+    one_row = rows == 1 and not fsal
+    whole = not group and fusion in (AUTO, WHOLE)
+    rhs = boxed = _single(dev, y0)
+    if rhs is not None and one_row and hasattr(rhs, 'supports_coop'):
+        rhs = None                                   # adaptive_heun: the MLP tile kernels have no 1-row tableau - the cooperative kernel does
+    if rhs is None and whole:
+        if _tuple(func, y0) is not None:             # tuple state of a row-local RHS: one segmented buffer
+            return Route('fused_tuple', dev, _TUPLE_WHY)
+        if _coop(dev, y0, any_box=one_row) is not None:
+            # a network outside the tile kernels' box (float64, wide): the cooperative whole-call kernel (it exists for every adaptive tableau)
+            return Route('fused_coop', dev, 'rhs.MLP.supports_coop: outside the tile kernels\' box (dim <= 64, hidden <= 128), inside the '
+                         'cooperative kernel\'s (<= 256 wide) and under COOP_MAX_FMA multiply-adds per evaluation')
+    # dopri8 (13 rows) and adaptive_heun (1 row, not FSAL shaped): row-local kernels only, no per-stage schedule
+    wide_ok = ((fsal and rows == 13) or one_row) and fusion != STAGE and (
+        getattr(rhs, 'row_local', False) or getattr(rhs, 'wide_tableaus', False) or (rows == 13 and getattr(rhs, 'tile_dopri8', False)))
+    if rhs is not None and (wide_ok or (fsal and rows in (3, 6))):
+        return Route('fused', rhs, 'supports(y0)')
+    if boxed is not None:
+        why = 'the %d-row tableau exists for row-local / cooperative right-hand sides%s only' % (rows, ' and the tile kernels' if rows == 13 else '')
+    elif getattr(func, 'per_component', False):
+        why = 'rhs.PerComponent shares one buffer on the whole-call schedule only (2 .. %d components, row-local, no process group)' % N.MAX_SEGMENTS
+    else:
+        why = '%s.supports(y0) is False (dim %s, dtype %s)' % (type(dev).__name__, dev.dim, getattr(y0[0], 'dtype', None))
+    # (e.g. hidden > 256: no kernel of the family takes it - the descriptor says so once)
+    told = rhs is None and whole and len(y0) == 1 and hasattr(dev, 'warn_limits') and isinstance(y0[0], torch.Tensor) and not dev.coop_in_box(y0[0])
+    return host(why, dev if told else None)
+
+
+def multistep(func, y0, refused=''):
+    """The Adams solvers: one launch (csrc/mi_ode_adams.h, mi_ode_adams_vc.h) or the per-step loop.  refused: the option that rules it out."""
+    dev = getattr(func, 'device_rhs', None)
+    rhs = None if refused else _single(dev, y0, multistep=True)
+    if rhs is not None and getattr(rhs, 'multistep_fused', False):
+        return Route('fused_multistep', rhs, 'multistep_fused: row-local systems, matrix right-hand sides and networks up to 256 wide')
+    return Route('planes', None, _PYTHON[len(y0) == 1] if dev is None else refused or 'no one-launch multistep kernel for this right-hand side')
+
+
+def fixed_grid(func, y0, name, *, one_launch, default_grid=True, eps=0.0, fusion=AUTO):
+    """The fixed-grid Runge-Kutta solvers.  one_launch: the method has a fused kernel (euler, rk4); default_grid: the steps are on `t` itself."""
+    dev = getattr(func, 'device_rhs', None)
+    own_grid = not (default_grid and eps == 0.0)
+    kind, rhs = 'fused', _single(dev, y0) if one_launch else None
+    if rhs is None and one_launch:
+        # a network outside the tile kernels' box (float64, wide): euler / rk4 on the cooperative one-launch kernel
+        kind, rhs = 'fused_coop', _coop(dev, y0)
+    if rhs is None and one_launch and not own_grid and getattr(_tuple(func, y0), 'fixed_grid_fused', False):
+        # a tuple state of a row-local RHS: a fixed grid has no norms, so the components simply share one buffer and the one-launch kernel
+        return Route('fused_tuple', dev, _TUPLE_WHY)
+    if rhs is not None and rhs.fixed_grid_fused and not (own_grid and fusion == STAGE):
+        return Route(kind, rhs, 'euler / rk4 have one-launch fixed-grid kernels for every fused family')
+    if dev is None:
+        return Route('planes', None, _PYTHON[len(y0) == 1])
+    if not one_launch:
+        return Route('planes', None, '%s has no fused kernel (euler / rk4 do)' % name)
+    return Route('planes', None, 'a grid of its own (step_size / grid_constructor / eps) on the per-stage schedule: the grid-walking kernel '
+                 'is whole-call' if rhs is not None and rhs.fixed_grid_fused else 'no fixed-grid kernel takes this state')
+
+
+def not_traced(opts, mode):
+    """'' when the options leave a Python callable to the tracer (lower.py), else why they do not.  mode: options['lower']."""
+    if mode is False or mode == 'off':
+        return "options['lower'] is False"
+    asks = ('process_group', 'force_plane_kernels', 'grid_constructor')
+    if any(k in opts for k in asks) or (opts.get('graph', 'auto') != 'auto' and mode is not True):
+        return 'an option asks for one of the callable engines (%s)' % sorted(k for k in opts if k in asks + ('graph',))
+    return ''

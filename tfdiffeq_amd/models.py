@@ -9,6 +9,7 @@ included: the stage time only shifts the first layer's bias) and training on it 
 import torch
 from torch import nn
 
+from . import dispatch as _dispatch
 from . import rhs as _rhs
 from .adjoint import odeint_adjoint
 from .odeint import odeint
@@ -149,7 +150,7 @@ class ODEBlock(nn.Module):
             else:
                 # (the tile kernels, or - float64 / wider networks, round 5 - the cooperative one-launch kernel; if neither takes the problem
                 # the solver runs the descriptor's own forward() as a callable on the device-controlled engine and says so once)
-                func = fused if (fused is not None and (fused.supports(x_aug) or fused.supports_coop(x_aug))) else self.odefunc
+                func = fused if (fused is not None and _dispatch.has_kernel(fused, x_aug)) else self.odefunc
             with torch.no_grad():
                 out = odeint(func, x_aug, integration_time, **kw)                           # :184-186
             if func is fused:                                    # f ran inside the kernel: the counter the reference exposes

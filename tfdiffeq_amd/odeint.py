@@ -4,6 +4,7 @@ import os
 from .adams import VariableCoefficientAdamsBashforth
 from .adaptive_huen import AdaptiveHeunSolver
 from .bosh3 import Bosh3Solver
+from .dispatch import not_traced
 from .dopri5 import Dopri5Solver
 from .dopri8 import Dopri8Solver
 from .fixed_adams import AdamsBashforth, AdamsBashforthMoulton
@@ -130,9 +131,6 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
 # tests of the callable engines set it to False so that their Python callables stay Python callables.
 LOWER_DEFAULT = False if os.environ.get('TFDIFFEQ_AMD_LOWER', '1').lower() in ('0', 'false', 'off') else 'auto'
 
-_LOWER_METHODS = ('dopri5', 'tsit5', 'bosh3', 'dopri8', 'adaptive_heun', 'euler', 'rk4', 'midpoint', 'heun', 'huen', 'explicit_adams',
-                  'fixed_adams', 'adams')
-
 
 def _descriptor(func):
     """A DeviceRHS: a catalogue descriptor (`kind`) or one with a fused stage of its own (rhs.Conv2dODE, kind 0) - never traced."""
@@ -147,45 +145,36 @@ def _try_lower(func, y0, method, options):
     import torch
     opts = options or {}
     mode = opts.get('lower', LOWER_DEFAULT)
-    if mode is False or mode == 'off' or not callable(func) or _descriptor(func) or getattr(func, 'per_component', False):
+    if not callable(func) or _descriptor(func) or getattr(func, 'per_component', False) or not_traced(opts, mode):
         return None
-    if method is not None and method not in _LOWER_METHODS:
-        return None
-    if any(k in opts for k in ('process_group', 'force_plane_kernels', 'grid_constructor')) or (opts.get('graph', 'auto') != 'auto' and mode is not True):
+    if method is not None and method not in SOLVERS:
         return None
     y = y0[0] if isinstance(y0, (tuple, list)) and len(y0) == 1 else y0
     from . import lower as _lower
-    if isinstance(y, (tuple, list)):
+    several = isinstance(y, (tuple, list))
+    if several:
         # a tuple state of several components (tests/api_tests.py:29-34): lowered when every component follows the same trajectory-local
         # function (rhs.PerComponent: one launch, one error ratio per component); anything else keeps its Python loop
         ok = 2 <= len(y) <= 8 and all(isinstance(c, torch.Tensor) and c.is_cuda and c.dtype == y[0].dtype and c.numel() > 0 and
                                       c.dtype in (torch.float32, torch.float64) for c in y) and method in (None, 'dopri5', 'bosh3', 'tsit5', 'euler', 'rk4')
         if not ok:
             return None
-        try:
-            return _lower.lower_tuple(func, y, method=method), None
-        except _lower.TraceError as e:
-            why = str(e)
-        except Exception as e:
-            why = 'tracing failed: %s: %s' % (type(e).__name__, e)
-        if mode is True:
-            raise ValueError('odeint(options={\'lower\': True}): this callable cannot be lowered onto the fused kernels: ' + why)
-        return None, why
-    if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dtype not in (torch.float32, torch.float64) or y.numel() == 0:
+    elif not isinstance(y, torch.Tensor) or not y.is_cuda or y.dtype not in (torch.float32, torch.float64) or y.numel() == 0:
         return None
     wrapped = func
-    if y is not y0:                                       # a one-component tuple (the adjoint's forward pass): the tensor form of the same system
+    if not several and y is not y0:                                       # a one-component tuple (the adjoint's forward pass): the tensor form of the same system
         def wrapped(t_, y_, _f=func):
             return _f(t_, (y_,))[0]
     try:
-        return _lower.lower(wrapped, y, method=method), None
+        return (_lower.lower_tuple(func, y, method=method) if several else _lower.lower(wrapped, y, method=method)), None
     except _lower.TraceError as e:
         why = str(e)
     except Exception as e:                                # the callable itself failed on the proxies (an operation torch refuses for them)
         why = 'tracing failed: %s: %s' % (type(e).__name__, e)
     if mode is True:
         raise ValueError('odeint(options={\'lower\': True}): this callable cannot be lowered onto the fused kernels: ' + why)
-    _warn_once('odeint: `func` runs as a Python callable between library kernels (not lowered onto the fused kernels: %s)' % why)
+    if not several:
+        _warn_once('odeint: `func` runs as a Python callable between library kernels (not lowered onto the fused kernels: %s)' % why)
     return None, why
 
 
@@ -367,10 +356,6 @@ def _callable_module(func, mods=(), tens=()):
         def forward(self, t, y):
             return self._f(t, y)
     return _M(func)
-
-
-def _CallableModule(func):
-    return _callable_module(func)
 
 
 def _warn_once(msg):

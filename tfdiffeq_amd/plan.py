@@ -1,70 +1,66 @@
-"""`odeint.plan(func, y0, t, ...)`: which engine a call will take and the predicate that chose it - BEFORE running it (round-5 review,
-item 9: the dispatch between the engines is spread over `supports*` predicates of rhs.py and the solver classes; this is the one table).
+"""`odeint.plan(func, y0, t, ...)`: which engine a call will take and the predicate that chose it - BEFORE running it, with or without a GPU.
 
-Nothing is launched and no engine is created: the answer is derived from the same predicates `solvers.py` / `adams.py` evaluate
-(`DeviceRHS.supports`, `.supports_coop`, `.supports_multistep`, `.row_local`, `.tile_dopri8`, `.wide_tableaus`, `.fixed_grid_fused`,
-`.multistep_fused`, the tableau's shape), so it also works where there is no GPU (the state's device is then taken as given).  The one
-thing decided later, inside `mi_ode_create`, is co-residency: a whole-call kernel needs every workgroup of the batch resident at once;
-`plan` reports the rule ('co-resident batch') rather than the device's answer.
+The decision is not made here: `plan` constructs the solver `odeint` would construct and formats `solver.route()` (tfdiffeq_amd/dispatch.py, what
+`integrate` itself consumes).  This module adds the name of the C++ kernel instantiation per route kind and family (csrc `pick_family` stays the
+authority for C-ABI callers) and the launch count.  Co-residency is decided later, inside `mi_ode_create`: `plan` reports the rule and
+`dispatch.after(route)` rather than the device's answer.
 
     >>> odeint.plan(lambda t, y: torch.matmul(y, W), y0, t, method='dopri5')
     {'engine': 'fused', 'family': 'linear', 'kernel': 'k_persist_linear_mfma<double, 128, 6>', 'launches': 'one per call', ...}
 """
 import torch
 
+from . import dispatch as D
 from . import rhs as R
+from .fixed_adams import AdamsBashforthMoulton
+from .misc import _TupleFunc
+from .solvers import FixedGridODESolver, _AdaptiveRKSolver
 
-ADAPTIVE = {'dopri5': (6, True), 'tsit5': (6, True), 'bosh3': (3, True), 'dopri8': (13, True), 'adaptive_heun': (1, False)}   # rows, FSAL shaped
-FIXED_RK = {'euler': True, 'rk4': True, 'midpoint': False, 'heun': False, 'huen': False}                                           # has a one-launch kernel
-MULTISTEP = ('explicit_adams', 'fixed_adams', 'adams')
-
-
-def _tname(dtype):
-    return 'double' if dtype == torch.float64 else 'float'
-
-
-def _family(rhs):
-    if isinstance(rhs, R.MLP):
-        return 'mlp'
-    if isinstance(rhs, R.CubicLinear):
-        return 'cubic_linear'
-    if isinstance(rhs, R.Linear):
-        return 'linear'
-    if getattr(rhs, 'coop', False) or isinstance(rhs, R.CustomCoop):
-        return 'generated / user code, a thread per state element'
-    if getattr(rhs, 'row_local', False):
-        return 'row-local (a trajectory per thread)'
-    return type(rhs).__name__
-
-
-def _callable_engine(method, options, why):
-    opts = options or {}
-    if method in ADAPTIVE and opts.get('graph', 'auto') != 'host' and not opts.get('force_plane_kernels') and 'process_group' not in opts:
-        return {'engine': 'callable', 'kernel': 'k_opq_norms + k_opq_commit around torch kernels (graph_step.DeviceControlledRK)',
-                'launches': 'one hipGraph replay per attempt once recorded (options graph=%r), eager before' % (opts.get('graph', 'auto'),),
-                'why': why}
-    return {'engine': 'plane kernels', 'kernel': 'mi_ode_lincomb / mi_ode_error_norms / mi_ode_interp_eval between evaluations of f',
-            'launches': 'several per stage, the controller on the host', 'why': why}
+TNAME = {torch.float32: 'float', torch.float64: 'double'}
+ENGINE = {'callable': 'callable', 'planes': 'plane kernels'}          # (every other route kind: 'fused')
+FAMILY = {'rowlocal': 'row-local (a trajectory per thread)', 'coop': 'generated / user code, a thread per state element'}     # as displayed
+# what a 'callable' route, and a 'planes' route of each solver family, runs on: (kernel, launches)
+HOST = {'callable': ('k_opq_norms + k_opq_commit around torch kernels (graph_step.DeviceControlledRK)',
+                     'one hipGraph replay per attempt once recorded (options graph=%r), eager before'),
+        _AdaptiveRKSolver: ('mi_ode_lincomb / mi_ode_error_norms / mi_ode_interp_eval between evaluations of f', 'several per stage, the controller on the host'),
+        AdamsBashforthMoulton: ('mi_ode_lincomb', 'several per step'),
+        FixedGridODESolver: ('step_func over mi_ode_lincomb, one evaluation of forward() per stage', 'several per grid interval'),
+        object: ('k_adams_predict / _correct / _error_sums / _update_phi', 'four per attempt')}
+# the 'fused' route of an adaptive Runge-Kutta call on a family with ONE kernel: (kernel, launches, why); formatted with T, S, A, M
+ADAPTIVE = {'rowlocal': ('k_persist_rowlocal<{T}, {S}, ..> (k_persist_rowlocal_planes beyond 131072 trajectories)', 'one per call',
+                         'row_local right-hand side: state and stage derivatives thread-private'),
+            'coop': ('k_persist_rowlocal<{T}, {S}, .., RhsUserCoop> (planes variant beyond a co-resident batch)', 'one per call',
+                     'cooperative plugin: a thread per state element, dim <= 256'),
+            'mlp': ('k_persist_mlp{M}<DP, HP, {A}, {S}> (dim / hidden padded; k_mlp per attempt when the tile grid is not co-resident)', 'one per call',
+                    'rhs.MLP.supports: dim <= 64, hidden <= 128 - the MFMA tile kernels (float32: weights resident in registers; '
+                    'float64: weights streamed from a packed copy)'),
+            # (y ** 3) @ W beyond 2 x 2: csrc pick_family keeps the cube on the vector-ALU stage kernels
+            'cubic_linear': ('k_stage_linear_valu', 'one per stage', '(y ** 3) @ W: the tile kernels have no cube in front of the product (measured in round 6: '
+                             'a run-time switch for it costs the linear system 1.4 % at config 4) - the vector-ALU stage kernels, dim <= 256')}
 
 
-def plan_conv(rhs, y, method, options=None):
+def _host(solver, route, opts, why=None):
+    """A 'callable' / 'planes' route, formatted."""
+    key = 'callable' if route.kind == 'callable' else next(k for k in HOST if isinstance(k, type) and isinstance(solver, k))
+    return {'engine': ENGINE[route.kind], 'kernel': HOST[key][0], 'launches': HOST[key][1].replace('%r', repr(opts.get('graph', 'auto'))),
+            'why': route.why if why is None else why}
+
+
+def plan_conv(rhs, y, solver, route, opts):
     """rhs.Conv2dODE: the fused stage kernel (csrc/mi_ode_conv.h) inside its box, the torch module on the callable engine outside."""
-    why = rhs.in_box(y)
-    base = {'family': 'conv2d', 'box': 'NCHW float32 / float64, C <= %d, F <= %d, relu / softplus / tanh, any H, W, batch' % (rhs.MAX_C, rhs.MAX_F)}
+    why, rk = rhs.in_box(y), isinstance(solver, _AdaptiveRKSolver)
     if why:
-        d = _callable_engine(method, options, 'rhs.Conv2dODE outside the fused kernel\'s box (%s): the torch module runs' % why)
-    elif method in ADAPTIVE:
-        d = _callable_engine(method, options, 'rhs.Conv2dODE: each Runge-Kutta stage (stage state + three convolutions) is one launch')
-        if d['engine'] == 'callable':                    # (graph='host', force_plane_kernels, process_group: the host loop calls f per stage)
-            d['kernel'] = 'k_conv_stage<%s> per stage + k_opq_norms + k_opq_commit (graph_step.DeviceControlledRK)' % _tname(y.dtype)
-        else:
-            d['kernel'] = 'k_conv_stage<%s> per evaluation of f, plane kernels between' % _tname(y.dtype)
-            d['why'] = 'rhs.Conv2dODE on the host-controlled loop (the options ask for it): one fused evaluation per stage'
-    else:
-        d = {'engine': 'plane kernels', 'kernel': 'k_conv_stage<%s> per evaluation of f, plane kernels between' % _tname(y.dtype),
-             'launches': 'one per evaluation of f plus the solver\'s state arithmetic', 'why': 'rhs.Conv2dODE on a fixed-grid / multistep method'}
-    d.update(base)
-    d['fused_stage'] = not why
+        d = _host(solver, route, opts, 'rhs.Conv2dODE outside the fused kernel\'s box (%s): the torch module runs' % why)
+    elif route.kind == 'callable':
+        d = _host(solver, route, opts, 'rhs.Conv2dODE: each Runge-Kutta stage (stage state + three convolutions) is one launch')
+        d['kernel'] = 'k_conv_stage<%s> per stage + k_opq_norms + k_opq_commit (graph_step.DeviceControlledRK)' % TNAME[y.dtype]
+    else:                                                # (graph='host', force_plane_kernels, process_group: the host loop calls f per stage)
+        d = _host(solver, route, opts, 'rhs.Conv2dODE on the host-controlled loop (the options ask for it): one fused evaluation per stage'
+                  if rk else 'rhs.Conv2dODE on a fixed-grid / multistep method')
+        d['kernel'] = 'k_conv_stage<%s> per evaluation of f, plane kernels between' % TNAME[y.dtype]
+        d['launches'] = d['launches'] if rk else 'one per evaluation of f plus the solver\'s state arithmetic'
+    d.update(family='conv2d', fused_stage=not why,
+             box='NCHW float32 / float64, C <= %d, F <= %d, relu / softplus / tanh, any H, W, batch' % (rhs.MAX_C, rhs.MAX_F))
     if not why:
         d['odeblock'] = ('fused stage kernel' if rhs.faster_than_torch(y) else
                          'torch module: %.3g GFLOP of conv2 per evaluation > %.3g, where the fused kernel measured slower than torch'
@@ -72,143 +68,88 @@ def plan_conv(rhs, y, method, options=None):
     return d
 
 
-def plan_rhs(rhs, y, method, options=None):
-    """The decision for a DeviceRHS and ONE state tensor (shape / dtype are read, nothing else)."""
-    opts = options or {}
-    fusion = opts.get('fusion', 0)
-    rows = y.numel() // max(int(rhs.dim or 1), 1)
-    T = _tname(y.dtype)
-    fam = _family(rhs)
-    base = {'family': fam, 'state': '%d x %d %s' % (rows, rhs.dim, str(y.dtype).replace('torch.', ''))}
-    coop_ok = hasattr(rhs, 'supports_coop') and rhs.supports_coop(y)
+def _linear_kernel(dim, T, S, fusion):
+    """(kernel, launches, why) of rhs.Linear on the 'fused' route of an adaptive Runge-Kutta call: the tier csrc `pick_family` picks."""
+    per = {D.STAGE: 'stage', D.STEP: 'attempt'}.get(fusion)
+    if 3 <= dim <= 128 or (128 < dim <= 256 and S in (3, 6) and fusion != D.STAGE):
+        tile = 256 if dim > 128 else max(16, 1 << (dim - 1).bit_length())
+        kernel = 'k_%s_linear_mfma<%s, %d, %d> (one kernel per %s)' % ('step' if per == 'attempt' else 'stage', T, tile, S, per) if per else \
+            'k_persist_linear_mfma<%s, %d, %d> (co-resident batch; k_step_linear_mfma per attempt otherwise)' % (T, tile, S)
+        return kernel, 'per %s' % per if per else 'one per call', (
+            '3 <= dim <= 128: the MFMA tile kernels (W slice resident in registers)' if dim <= 128 else
+            '128 < dim <= 256, three- or six-row tableau: the 256-wide MFMA tile kernels (W streamed from a copy in consumption order, '
+            'csrc/mi_ode_step_fused.h LinCtx::STREAM)')
+    return ('k_stage_linear_valu', 'one per stage',
+            'dim %d outside 3 .. 128 (and not a dopri5 / tsit5 / bosh3 call at dim <= 256): the vector-ALU fallback (dim <= 256)' % dim)
 
-    def out(d):
-        d.update(base)
-        return d
-    if opts.get('force_plane_kernels'):
-        return out(_callable_engine(method, opts, "options['force_plane_kernels']"))
-    if method in ADAPTIVE:
-        S, fsal = ADAPTIVE[method]
-        if not rhs.supports(y):
-            if coop_ok and 'process_group' not in opts and fusion in (0, 'auto', 4, 'whole'):
-                return out({'engine': 'fused', 'kernel': 'k_persist_rowlocal<%s, %d, .., RhsMlpCoop> (planes variant beyond a co-resident batch)' % (T, S),
-                            'launches': 'one per call', 'why': 'rhs.MLP.supports_coop: outside the tile kernels\' box (dim <= 64, hidden <= 128), '
-                            'inside the cooperative kernel\'s (<= 256 wide) and under COOP_MAX_FMA multiply-adds per evaluation'})
-            return out(_callable_engine(method, opts, '%s.supports(y0) is False (dim %s, dtype %s)' % (type(rhs).__name__, rhs.dim, y.dtype)))
-        wide = (fsal and S == 13) or (not fsal and S == 1)
-        if wide:
-            ok = getattr(rhs, 'row_local', False) or getattr(rhs, 'wide_tableaus', False) or (S == 13 and getattr(rhs, 'tile_dopri8', False))
-            if not ok or fusion in (1, 'stage'):
-                return out(_callable_engine(method, opts, 'the %d-row tableau exists for row-local / cooperative right-hand sides%s only'
-                                            % (S, ' and the tile kernels' if S == 13 else '')))
-        if getattr(rhs, 'row_local', False):
-            return out({'engine': 'fused', 'kernel': 'k_persist_rowlocal<%s, %d, ..> (k_persist_rowlocal_planes beyond 131072 trajectories)' % (T, S),
-                        'launches': 'one per call', 'why': 'row_local right-hand side: state and stage derivatives thread-private'})
-        if getattr(rhs, 'coop', False) or isinstance(rhs, R.CustomCoop):
-            return out({'engine': 'fused', 'kernel': 'k_persist_rowlocal<%s, %d, .., RhsUserCoop> (planes variant beyond a co-resident batch)' % (T, S),
-                        'launches': 'one per call', 'why': 'cooperative plugin: a thread per state element, dim <= 256'})
-        if fam == 'mlp':
-            kern = 'k_persist_mlp' if y.dtype == torch.float32 else 'k_persist_mlp64'
-            return out({'engine': 'fused', 'kernel': '%s<DP, HP, %d, %d> (dim / hidden padded; k_mlp per attempt when the tile grid is not co-resident)'
-                        % (kern, R.MLP.ACTIVATIONS[rhs.activation], S), 'launches': 'one per call',
-                        'why': 'rhs.MLP.supports: dim <= 64, hidden <= 128 - the MFMA tile kernels (float32: weights resident in registers; '
-                               'float64: weights streamed from a packed copy)'})
-        if fam in ('linear', 'cubic_linear'):
-            if fam == 'cubic_linear':                # (y ** 3) @ W beyond 2 x 2: csrc pick_family keeps the cube on the vector-ALU stage kernels
-                return out({'engine': 'fused', 'kernel': 'k_stage_linear_valu', 'launches': 'one per stage',
-                            'why': '(y ** 3) @ W at dim %d: the tile kernels have no cube in front of the product (measured in round 6: a run-time '
-                                   'switch for it costs the linear system 1.4 %% at config 4) - the vector-ALU stage kernels, dim <= 256' % rhs.dim})
-            if 3 <= rhs.dim <= 128:
-                sched = {1: 'k_stage_linear_mfma (one kernel per stage)', 'stage': 'k_stage_linear_mfma (one kernel per stage)',
-                         2: 'k_step_linear_mfma (one kernel per attempt)', 'step': 'k_step_linear_mfma (one kernel per attempt)'}.get(
-                             fusion, 'k_persist_linear_mfma<%s, %d, %d> (co-resident batch; k_step_linear_mfma per attempt otherwise)'
-                             % (T, max(16, 1 << (int(rhs.dim) - 1).bit_length()), S))
-                return out({'engine': 'fused', 'kernel': sched, 'launches': 'one per call' if fusion in (0, 'auto', 4, 'whole') else 'per stage / attempt',
-                            'why': '3 <= dim <= 128: the MFMA tile kernels (W slice resident in registers)'})
-            if fam == 'linear' and 128 < rhs.dim <= 256 and S in (3, 6) and fusion not in (1, 'stage'):
-                sched = 'k_step_linear_mfma<%s, 256, %d> (one kernel per attempt)' % (T, S) if fusion in (2, 'step') else \
-                    'k_persist_linear_mfma<%s, 256, %d> (co-resident batch; k_step_linear_mfma per attempt otherwise)' % (T, S)
-                return out({'engine': 'fused', 'kernel': sched, 'launches': 'one per call' if fusion in (0, 'auto', 4, 'whole') else 'per attempt',
-                            'why': '128 < dim <= 256, three- or six-row tableau: the 256-wide MFMA tile kernels (W streamed from a copy in '
-                                   'consumption order, csrc/mi_ode_step_fused.h LinCtx::STREAM)'})
-            return out({'engine': 'fused', 'kernel': 'k_stage_linear_valu', 'launches': 'one per stage',
-                        'why': 'dim %d outside 3 .. 128 (and not a dopri5 / tsit5 / bosh3 call at dim <= 256): the vector-ALU fallback (dim <= 256)' % rhs.dim})
-        return out({'engine': 'fused', 'kernel': 'catalogue kernels of %s' % type(rhs).__name__, 'launches': 'one per call', 'why': 'supports(y0)'})
-    if method in FIXED_RK:
-        if FIXED_RK[method] and rhs.fixed_grid_fused and (rhs.supports(y) or coop_ok):
-            k = 'k_fixed_rowlocal' if (getattr(rhs, 'row_local', False) or getattr(rhs, 'coop', False) or isinstance(rhs, R.CustomCoop) or coop_ok) else \
-                ('k_fixed_mlp' if fam == 'mlp' else 'k_fixed_linear_mfma' if (fam == 'linear' and 3 <= rhs.dim <= 256) else 'FX_* stage kernels (vector ALU)')
-            return out({'engine': 'fused', 'kernel': '%s<%s, ..>' % (k, T), 'launches': 'one per call',
-                        'why': 'euler / rk4 have one-launch fixed-grid kernels for every fused family'})
-        return out({'engine': 'plane kernels', 'kernel': 'step_func over mi_ode_lincomb, one evaluation of forward() per stage',
-                    'launches': 'several per grid interval', 'why': '%s has no fused kernel (euler / rk4 do)' % method if not FIXED_RK[method]
-                    else 'no fixed-grid kernel takes this state'})
-    if method in MULTISTEP:
-        if rhs.supports_multistep(y) and getattr(rhs, 'multistep_fused', False):
-            k = 'k_adams_vc_rowlocal' if method == 'adams' else 'k_fixed_adams_rowlocal'
-            return out({'engine': 'fused', 'kernel': '%s<%s, ..>' % (k, T), 'launches': 'one per call (co-resident batch; the per-step loop otherwise)',
-                        'why': 'multistep_fused: row-local systems, matrix right-hand sides and networks up to 256 wide'})
-        return out({'engine': 'plane kernels', 'kernel': 'k_adams_predict / _correct / _error_sums / _update_phi' if method == 'adams' else 'mi_ode_lincomb',
-                    'launches': 'four per attempt' if method == 'adams' else 'several per step', 'why': 'no one-launch multistep kernel for this right-hand side'})
-    raise KeyError(method)
+
+def plan_rhs(rhs, y, solver, route, opts):
+    """A DeviceRHS and ONE state tensor: the solver's route, formatted (shape / dtype are read, nothing else)."""
+    T, fam, kind = TNAME[y.dtype], D.family(rhs), route.kind
+    d = {'engine': ENGINE.get(kind, 'fused'), 'launches': 'one per call', 'why': route.why}
+    if kind in ENGINE:
+        d = _host(solver, route, opts)
+    elif kind == 'fused_multistep':
+        d['kernel'] = '%s<%s, ..>' % ('k_fixed_adams_rowlocal' if isinstance(solver, FixedGridODESolver) else 'k_adams_vc_rowlocal', T)
+        d['launches'] = 'one per call (co-resident batch; %s otherwise)' % ENGINE[D.after(route).kind]
+    elif isinstance(solver, FixedGridODESolver):
+        k = 'k_fixed_rowlocal' if (fam in ('rowlocal', 'coop') or kind == 'fused_coop') else \
+            ('k_fixed_mlp' if fam == 'mlp' else 'k_fixed_linear_mfma' if (fam == 'linear' and 3 <= rhs.dim <= 256) else 'FX_* stage kernels (vector ALU)')
+        d['kernel'] = '%s<%s, ..>' % (k, T)
+    elif kind == 'fused_coop':
+        d['kernel'] = 'k_persist_rowlocal<%s, %d, .., RhsMlpCoop> (planes variant beyond a co-resident batch)' % (T, len(solver.tableau.alpha))
+    else:                                               # the family's own sentence says which of its kernels, and why
+        S = len(solver.tableau.alpha)
+        k = _linear_kernel(int(rhs.dim), T, S, solver._fusion) if fam == 'linear' else ADAPTIVE.get(fam, ('catalogue kernels of ' + fam, 'one per call', route.why))
+        fmt = dict(T=T, S=S, M='' if y.dtype == torch.float32 else '64', A=R.MLP.ACTIVATIONS.get(getattr(rhs, 'activation', None)))
+        d.update(kernel=k[0].format(**fmt) if fam != 'linear' else k[0], launches=k[1], why=k[2])
+    d.update(family=FAMILY.get(fam, fam), state='%d x %d %s' % (y.numel() // max(int(rhs.dim or 1), 1), rhs.dim, str(y.dtype).replace('torch.', '')))
+    return d
 
 
 def plan(func, y0, t=None, rtol=1e-7, atol=1e-9, method=None, options=None):
     """What `odeint(func, y0, t, rtol, atol, method, options)` will run on.  A dict: engine ('fused' | 'callable' | 'plane kernels'),
     kernel, launches, why (the predicate that decided), family / state, and `lower` (how a Python callable was lowered, or why not)."""
     from . import lower as L
-    from . import odeint as _pkg_odeint              # noqa: F401  (the package exports the function under the module's name)
-    import sys
-    OD = sys.modules['tfdiffeq_amd.odeint']
+    from .odeint import LOWER_DEFAULT, SOLVERS       # (the submodule: the package exports the function under its name)
     method = method or 'dopri5'
     opts = dict(options or {})
-    if method not in OD.SOLVERS:
-        raise KeyError(method)
-    ys = y0 if isinstance(y0, (tuple, list)) else (y0,)
-    lower_info = None
+    mode = opts.pop('lower', LOWER_DEFAULT)
+    tensor_input = isinstance(y0, torch.Tensor)
+    ys = (y0,) if tensor_input else tuple(y0)
+
+    def routed(f, state, lift=tensor_input):
+        """The solver `odeint` constructs for this call (misc._check_inputs, odeint.py) and the route it takes."""
+        solver = SOLVERS[method](_TupleFunc(f) if lift else f, state, rtol=rtol, atol=atol, **opts)
+        return solver, solver.route()
+    why_not = None
     if getattr(func, 'stage_rhs', None) is not None and len(ys) == 1:
-        d = plan_conv(func.stage_rhs, ys[0], method, opts)
-        d['lower'] = None
-        return d
-    rhs = func if getattr(func, 'kind', 0) else None
-    if rhs is None and getattr(func, 'per_component', False):
-        base = func.device_rhs
-        d = {'engine': 'fused' if (method in ADAPTIVE or FIXED_RK.get(method)) and getattr(base, 'row_local', False) and 2 <= len(ys) <= 8 else 'plane kernels',
-             'kernel': 'k_persist_rowlocal over one segmented buffer', 'launches': 'one per call',
-             'why': 'rhs.PerComponent of a row-local right-hand side: tuple components share one buffer', 'family': 'tuple of ' + _family(base)}
-        d['lower'] = None
-        return d
-    if rhs is None and len(ys) == 1 and isinstance(ys[0], torch.Tensor):
-        mode = opts.get('lower', OD.LOWER_DEFAULT)
-        if mode is False:
-            lower_info = {'lowered': False, 'why': "options['lower'] is False"}
-        elif any(k in opts for k in ('process_group', 'force_plane_kernels', 'grid_constructor')) or (opts.get('graph', 'auto') != 'auto' and mode is not True):
-            lower_info = {'lowered': False, 'why': 'an option asks for one of the callable engines (%s)' % sorted(k for k in opts if k in
-                                                                                                                ('process_group', 'force_plane_kernels', 'graph', 'grid_constructor'))}
-        else:
-            try:
-                tr = L.trace(func, ys[0])
+        return dict(plan_conv(func.stage_rhs, ys[0], *routed(func, ys), opts), lower=None)
+    if getattr(func, 'kind', 0) and len(ys) == 1:
+        return dict(plan_rhs(func, ys[0], *routed(func, ys), opts), lower=None)
+    if getattr(func, 'per_component', False):
+        solver, route = routed(func, ys)
+        d = _host(solver, route, opts) if route.kind != 'fused_tuple' else {
+            'engine': 'fused', 'launches': 'one per call', 'why': route.why,
+            'kernel': 'k_fixed_rowlocal over the concatenated components' if isinstance(solver, FixedGridODESolver) else 'k_persist_rowlocal over one segmented buffer'}
+        fam = D.family(func.device_rhs)
+        return dict(d, family='tuple of ' + FAMILY.get(fam, fam), lower=None)
+    if len(ys) == 1 and not getattr(func, 'kind', 0):
+        why_not, lowered = D.not_traced(opts, mode), None
+        # (a one-component tuple: `odeint` lowers the tensor form of the same system and re-enters with a tensor state, odeint.py `_try_lower`)
+        f1 = func if tensor_input else (lambda t_, y_: func(t_, (y_,))[0])
+        try:
+            if not why_not:
+                tr = L.trace(f1, ys[0])
                 prog = L.program_for(tr, generic=method in L.GENERIC_ONLY_METHODS)
-                kind = prog.kind
-                lower_info = {'lowered': True, 'kind': kind, 'dim': prog.dim, 'batch_axes': tr.nb}
-                shaped = ys[0].reshape(tr.batch_shape + (prog.dim,))
-                if kind in ('linear', 'cubic', 'mlp'):
-                    rhs = prog.bind(tr, ys[0].device)
-                else:
-                    rhs = prog.rhs
-                d = plan_rhs(rhs, shaped, method, opts)
-                d['lower'] = lower_info
-                return d
-            except L.TraceError as e:
-                lower_info = {'lowered': False, 'why': str(e)}
-            except Exception as e:
-                lower_info = {'lowered': False, 'why': 'tracing failed: %s: %s' % (type(e).__name__, e)}
-    if rhs is not None and len(ys) == 1:
-        d = plan_rhs(rhs, ys[0], method, opts)
-        d['lower'] = None
-        return d
-    why = 'a Python callable' + ('' if lower_info is None else ' (%s)' % lower_info['why']) if len(ys) == 1 else 'a tuple state of a Python callable'
-    d = _callable_engine(method, opts, why) if method in ADAPTIVE else \
-        {'engine': 'plane kernels', 'kernel': 'the solver\'s Python loop over plane kernels', 'launches': 'several per step', 'why': why}
-    d['lower'] = lower_info
-    return d
+                lowered = prog.bind(tr, ys[0].device) if prog.kind in ('linear', 'cubic', 'mlp') else prog.rhs
+        except L.TraceError as e:
+            why_not = str(e)
+        except Exception as e:
+            why_not = 'tracing failed: %s: %s' % (type(e).__name__, e)
+        if lowered is not None:
+            shaped = ys[0].reshape(tr.batch_shape + (prog.dim,))
+            return dict(plan_rhs(lowered, shaped, *routed(lowered, (shaped,), True), opts),
+                        lower={'lowered': True, 'kind': prog.kind, 'dim': prog.dim, 'batch_axes': tr.nb})
+    solver, route = routed(func, ys)
+    return dict(_host(solver, route, opts, route.why + (' (%s)' % why_not if why_not else '')), lower={'lowered': False, 'why': why_not} if why_not else None)

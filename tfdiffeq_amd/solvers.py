@@ -24,7 +24,9 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import dispatch as D
 from .misc import (_assert_increasing, _handle_unused_kwargs, _lincomb, _np_dtype, _scalar_tensor, _Exchange)
+from .rk_common import _is_fsal_shaped
 
 
 # ---------------------------------------------------------------------------------------------
@@ -35,7 +37,6 @@ def _fill_tableau(tb_struct, tableau, c_mid):
     if S > N.MAX_STAGES:
         raise ValueError('fused engine supports at most %d tableau rows' % N.MAX_STAGES)
     tb_struct.n_stages = S
-    from .rk_common import _is_fsal_shaped
     tb_struct.fsal = 1 if (S > 0 and _is_fsal_shaped(tableau)) else 0
     for i in range(S):
         tb_struct.alpha[i] = float(tableau.alpha[i])
@@ -121,7 +122,7 @@ class _FusedEngine(object):
         d.linear_variant = int(linear_variant)
         d.chunk_attempts = int(chunk_attempts)
         d.profile = 1 if profile else 0
-        d.fusion = {'auto': 0, 'stage': 1, 'step': 2, 'step_split': 3, 'whole': 4}.get(fusion, fusion)
+        d.fusion = D.FUSION.get(fusion, fusion)
         if multistep is not None and int(multistep[0]) == 3:       # the variable-order 'adams' solver in one launch: (3, max_order, gamma_star)
             d.multistep, d.ms_max_order = 3, int(multistep[1])
             self._ms_tabs = ((C.c_double * 13)(*[float(v) for v in multistep[2]][:13]),)
@@ -423,6 +424,17 @@ def _cached_engine_or_none(key, factory):
         return None
 
 
+def _one_launch(key, factory, run):
+    """(engine, run(engine)), or (None, None): not co-resident (remembered) or the grid hand-off timed out - nothing was committed."""
+    eng = _cached_engine_or_none(key, factory)
+    if eng is not None:
+        try:
+            return eng, run(eng)
+        except SyncTimeout:
+            pass
+    return None, None
+
+
 def _cached_engine(key, factory):
     eng = _ENGINE_CACHE.get(key)
     if eng is not None:
@@ -464,21 +476,6 @@ def _warn_once_coop(rhs, y, err):
                       'device-controlled engine instead' % (str(err).split(':')[-1].strip(),))
 
 
-def _fusable_tuple(func, y0):
-    """The row-local DeviceRHS behind a `rhs.PerComponent` lift if this tuple state can travel as one segmented buffer."""
-    rhs = getattr(func, 'device_rhs', None)
-    if rhs is None or not getattr(func, 'per_component', False) or not getattr(rhs, 'row_local', False):
-        return None
-    if not 2 <= len(y0) <= N.MAX_SEGMENTS:
-        return None
-    y = y0[0]
-    for c in y0:
-        if not (isinstance(c, torch.Tensor) and c.is_cuda and c.dim() >= 1 and c.numel() > 0 and c.dtype == y.dtype and
-                c.device == y.device and rhs.supports(c)):
-            return None
-    return rhs
-
-
 def _pack_components(y0, dim):
     """(packed [rows, dim] buffer, rows per component, row offset per component): every component starts on a multiple of
     _native.SEGMENT_ALIGN rows (include/mi_ode.h: mi_ode_desc.n_segments); padding rows are never touched by the kernels."""
@@ -491,19 +488,6 @@ def _pack_components(y0, dim):
     for c, r, o in zip(y0, rows, offs):
         packed[o:o + r].copy_(c.reshape(r, dim))
     return packed, rows, offs
-
-
-def _fusable(func, y0, multistep=False):
-    """The DeviceRHS behind `func` if the fused engine can run this problem, else None.  multistep: for the one-launch Adams kernels
-    (a family may take more there than on its Runge-Kutta kernels: rhs.MLP in float64 / up to 256 wide, round 5)."""
-    rhs = getattr(func, 'device_rhs', None)
-    if rhs is None or len(y0) != 1:
-        return None
-    y = y0[0]
-    ok = rhs.supports_multistep if multistep else rhs.supports
-    if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dim() >= 1 and y.numel() > 0 and ok(y)):
-        return None
-    return rhs
 
 
 # ---------------------------------------------------------------------------------------------
@@ -550,7 +534,8 @@ class FixedGridODESolver(object):
         unused_kwargs.pop('rtol', None)
         unused_kwargs.pop('atol', None)
         self._pg = unused_kwargs.pop('process_group', None)     # accepted for symmetry; fixed grid needs no exchange
-        self._fusion = unused_kwargs.pop('fusion', 0)
+        fusion = unused_kwargs.pop('fusion', 0)
+        self._fusion = D.FUSION.get(fusion, fusion)
         self._graph = bool(unused_kwargs.pop('graph', False))    # plane path: one captured step, replayed per grid interval
         _handle_unused_kwargs(self, unused_kwargs)
         del unused_kwargs
@@ -592,91 +577,91 @@ class FixedGridODESolver(object):
         """(kind, max_order, max_iters, min_order, ab, am, am0) for the one-launch multistep kernel, or None (fixed_adams.py sets it)."""
         return None
 
+    def route(self):
+        """The engine this call is routed to (dispatch.Route), decided without running anything."""
+        self._ms = self._fused_multistep()
+        if self._ms is not None:
+            return D.multistep(self.func, self.y0, "options fusion='stage' / graph=True ask for the per-step loop" if self._fusion == D.STAGE or self._graph else '')
+        return D.fixed_grid(self.func, self.y0, type(self).__name__.lower(), one_launch=self._fused_tableau is not None,
+                            default_grid=getattr(self, '_default_grid', False), eps=self.eps, fusion=self._fusion)
+
     def integrate(self, t):
         """solvers.py:82-104."""
         _assert_increasing(t)
-        t = t.to(self.y0[0].dtype)                    # :84 time in the STATE dtype here
-        ms = self._fused_multistep()
-        rhs = _fusable(self.func, self.y0) if ms is None else None      # (a multistep solver asks below, with the multistep kernels' own limits)
-        if rhs is None and ms is None and len(self.y0) == 1 and self._fused_tableau is not None:
-            # a network outside the tile kernels' box (float64, wide): euler / rk4 on the cooperative one-launch kernel (round 5)
-            cand = getattr(self.func, 'device_rhs', None)
-            y_ = self.y0[0]
-            if cand is not None and hasattr(cand, 'supports_coop') and isinstance(y_, torch.Tensor) and y_.is_cuda and y_.numel() > 0 and \
-                    cand.supports_coop(y_):
-                rhs = cand
-        default_grid = getattr(self, '_default_grid', False)
-        time_grid = None
-        if rhs is None and default_grid and self.eps == 0.0 and self._fused_tableau is not None:
-            # a tuple state of a row-local RHS (rhs.PerComponent): a fixed grid has no norms, so the components simply share one
-            # buffer (rows are independent trajectories) and the one-launch kernel
-            trhs = _fusable_tuple(self.func, self.y0)
-            if trhs is not None and trhs.fixed_grid_fused:
-                dim = trhs.dim
-                rows = [int(c.numel() // dim) for c in self.y0]
-                y = torch.cat([c.reshape(-1, dim) for c in self.y0], dim=0).contiguous()
-                key = ('fixed', trhs.cache_key(y.dtype, y.device), tuple(y.shape), y.dtype, str(y.device),
-                       _tableau_key(self._fused_tableau, None), self._fusion)
-                eng = _cached_engine(key, lambda: _FusedEngine(trhs, y, False, self._fused_tableau, fusion=self._fusion))
-                out = eng.integrate(t.to(torch.float64).numpy(), y)
-                self.stats = eng.stats.as_dict()
-                self.stats['components'] = len(rows)
-                offs = np.concatenate([[0], np.cumsum(rows)])
-                return tuple(out[:, int(o):int(o) + r].reshape((out.shape[0],) + tuple(c.shape)) for c, r, o in zip(self.y0, rows, offs[:-1]))
-        rhs_ms = _fusable(self.func, self.y0, multistep=True) if ms is not None else None     # (rhs.MLP: float64 / up to 256 wide here)
-        if rhs_ms is not None and getattr(rhs_ms, 'multistep_fused', False) and self._fusion not in (1, 'stage') and not self._graph:
-            rhs = rhs_ms
-            # the Adams family on a row-local catalogue system: the whole integration - history, predictor, corrector iterations and
-            # their batch-wide convergence test - in ONE launch (csrc/mi_ode_adams.h)
-            y = self.y0[0]
-            key = ('multistep', rhs.cache_key(y.dtype, y.device), tuple(y.shape), y.dtype, str(y.device), ms[:4], float(self.rtol), float(self.atol))
-            # (None: e.g. a batch whose workgroups cannot be co-resident - remembered - the per-step loop below)
-            eng = _cached_engine_or_none(key, lambda: _FusedEngine(rhs, y, False, _EULER_SHAPE, rtol=self.rtol, atol=self.atol, multistep=ms))
-            out = None
-            if eng is not None:
-                try:
-                    if default_grid and self.eps == 0.0:
-                        out = eng.integrate(t.to(torch.float64).numpy(), y)
-                    else:
-                        time_grid = self.grid_constructor(self.func, self.y0, t)
-                        assert bool(time_grid[0] == t[0]) and bool(time_grid[-1] == t[-1])        # solvers.py:87
-                        out = eng.integrate(t.to(torch.float64).numpy(), y, grid=time_grid.to(torch.float64).numpy(), eps=float(self.eps))
-                except SyncTimeout:                   # the grid hand-off timed out (shared GPU): nothing was committed, the per-step
-                    out = None                        # loop below does the same arithmetic
-            if out is not None:
-                self.stats = eng.stats.as_dict()
-                self.stats['engine'] = 'fused multistep kernel (one launch)'
-                for _ in range(int(self.stats.get('n_rejected', 0))):                         # fixed_adams.py:197-199
-                    print('Warning: Functional iteration did not converge. Solution may be incorrect.', file=sys.stderr)
-                return (out,)
-            rhs = None
-        if rhs is not None and rhs.fixed_grid_fused and self._fused_tableau is not None:
-            y = self.y0[0]
-            key = ('fixed', rhs.cache_key(y.dtype, y.device), tuple(y.shape), y.dtype, str(y.device),
-                   _tableau_key(self._fused_tableau, None), self._fusion)
-            # (a family that has no kernel for the requested schedule - the MLP with fusion='stage' has none: whole-attempt kernels
-            # only - takes the per-step loop below, as before its fixed-grid kernel existed; advisor, round 4)
-            eng = _cached_engine_or_none(key, lambda: _FusedEngine(rhs, y, False, self._fused_tableau, fusion=self._fusion))
-            if eng is not None and default_grid and self.eps == 0.0:
-                out = eng.integrate(t.to(torch.float64).numpy(), y)
-                self.stats = eng.stats.as_dict()
-                return (out,)
-            if eng is not None and self._fusion not in (1, 'stage'):
-                # a grid of its own (step_size / grid_constructor) and / or eps: still one launch - the kernel walks the grid
-                # and interpolates the requested times linearly inside the step that reaches them (solvers.py:86-115)
-                time_grid = self.grid_constructor(self.func, self.y0, t)
-                assert bool(time_grid[0] == t[0]) and bool(time_grid[-1] == t[-1])            # solvers.py:87
-                try:
-                    out = eng.integrate(t.to(torch.float64).numpy(), y, grid=time_grid.to(torch.float64).numpy(), eps=float(self.eps))
-                    self.stats = eng.stats.as_dict()
-                    return (out,)
-                except N.NativeError:
-                    pass                                  # no one-launch kernel for this family: the per-step loop below
-        if time_grid is None:
-            time_grid = self.grid_constructor(self.func, self.y0, t)
-        assert bool(time_grid[0] == t[0]) and bool(time_grid[-1] == t[-1])
         for y_ in self.y0:
             N.require_gpu_tensor(y_, 'y0')
+        t = t.to(self.y0[0].dtype)                    # :84 time in the STATE dtype here
+        route = self.route()
+        run = {'fused_tuple': self._integrate_tuple, 'fused_multistep': self._integrate_multistep, 'fused': self._integrate_single,
+               'fused_coop': self._integrate_single, 'planes': self._integrate_planes}[route.kind]
+        out = run(route.rhs, t)
+        if out is None:                               # dispatch.after(route): the per-step loop
+            out = self._integrate_planes(None, t)
+        self.stats['route'] = route.kind
+        return out
+
+    def _own_grid(self):
+        return not (getattr(self, '_default_grid', False) and self.eps == 0.0)
+
+    def _time_grid(self, t):
+        if getattr(self, '_grid', None) is None:      # (formed once per call: a fallback to the per-step loop reuses it)
+            self._grid = self.grid_constructor(self.func, self.y0, t)
+        assert bool(self._grid[0] == t[0]) and bool(self._grid[-1] == t[-1])              # solvers.py:87
+        return self._grid
+
+    def _integrate_on_grid(self, eng, t, y):
+        # one launch.  A grid of its own (step_size / grid_constructor) and / or eps: the kernel walks the grid and interpolates the
+        # requested times linearly inside the step that reaches them (solvers.py:86-115)
+        grid = self._time_grid(t).to(torch.float64).numpy() if self._own_grid() else None
+        return eng.integrate(t.to(torch.float64).numpy(), y, grid=grid, eps=float(self.eps))
+
+    def _integrate_tuple(self, rhs, t):
+        # a tuple state of a row-local RHS (rhs.PerComponent): a fixed grid has no norms, so the components simply share one
+        # buffer (rows are independent trajectories) and the one-launch kernel
+        dim = rhs.dim
+        rows = [int(c.numel() // dim) for c in self.y0]
+        y = torch.cat([c.reshape(-1, dim) for c in self.y0], dim=0).contiguous()
+        key = ('fixed', rhs.cache_key(y.dtype, y.device), tuple(y.shape), y.dtype, str(y.device),
+               _tableau_key(self._fused_tableau, None), self._fusion)
+        eng = _cached_engine(key, lambda: _FusedEngine(rhs, y, False, self._fused_tableau, fusion=self._fusion))
+        out = eng.integrate(t.to(torch.float64).numpy(), y)
+        self.stats = dict(eng.stats.as_dict(), components=len(rows))
+        offs = np.concatenate([[0], np.cumsum(rows)])
+        return tuple(out[:, int(o):int(o) + r].reshape((out.shape[0],) + tuple(c.shape)) for c, r, o in zip(self.y0, rows, offs[:-1]))
+
+    def _integrate_multistep(self, rhs, t):
+        # the Adams family on a row-local catalogue system: the whole integration - history, predictor, corrector iterations and
+        # their batch-wide convergence test - in ONE launch (csrc/mi_ode_adams.h)
+        y, ms = self.y0[0], self._ms
+        key = ('multistep', rhs.cache_key(y.dtype, y.device), tuple(y.shape), y.dtype, str(y.device), ms[:4], float(self.rtol), float(self.atol))
+        eng, out = _one_launch(key, lambda: _FusedEngine(rhs, y, False, _EULER_SHAPE, rtol=self.rtol, atol=self.atol, multistep=ms),
+                               lambda eng: self._integrate_on_grid(eng, t, y))
+        if eng is None:
+            return None
+        self.stats = dict(eng.stats.as_dict(), engine='fused multistep kernel (one launch)')
+        for _ in range(int(self.stats.get('n_rejected', 0))):                             # fixed_adams.py:197-199
+            print('Warning: Functional iteration did not converge. Solution may be incorrect.', file=sys.stderr)
+        return (out,)
+
+    def _integrate_single(self, rhs, t):
+        # (None: a family that has no kernel for the requested schedule - the MLP with fusion='stage' has none: whole-attempt kernels
+        # only - or for a grid of its own takes the per-step loop, as before its fixed-grid kernel existed; advisor, round 4)
+        y = self.y0[0]
+        key = ('fixed', rhs.cache_key(y.dtype, y.device), tuple(y.shape), y.dtype, str(y.device),
+               _tableau_key(self._fused_tableau, None), self._fusion)
+        eng = _cached_engine_or_none(key, lambda: _FusedEngine(rhs, y, False, self._fused_tableau, fusion=self._fusion))
+        if eng is None:
+            return None
+        try:
+            out = self._integrate_on_grid(eng, t, y)
+        except N.NativeError:
+            if not self._own_grid():
+                raise
+            return None
+        self.stats = eng.stats.as_dict()
+        return (out,)
+
+    def _integrate_planes(self, _, t):
         if self._graph and getattr(self, '_default_grid', False) and t.shape[0] > 1:
             # one captured step, replayed per grid interval with no host synchronisation in the loop (graph_step.py).
             # dt is formed in the state dtype on the host exactly like below (the values are exact in float64).
@@ -695,7 +680,7 @@ class FixedGridODESolver(object):
         solution = [self.y0]
         j = 1
         y0 = self.y0
-        grid = time_grid.numpy()
+        grid = self._time_grid(t).numpy()
         tt = t.numpy()
         for t0, t1 in zip(grid[:-1], grid[1:]):
             dy = self.step_func(self.func, t0, t1 - t0, y0)
@@ -704,6 +689,7 @@ class FixedGridODESolver(object):
                 solution.append(self._linear_interp(t0, t1, y0, y1, tt[j]))
                 j += 1
             y0 = y1
+        self.stats = {}
         return tuple(map(torch.stack, tuple(zip(*solution))))
 
     def _linear_interp(self, t0, t1, y0, y1, t):
@@ -748,7 +734,8 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
         if self._graph not in ('auto', 'host', 'reuse', True, False):
             raise ValueError("options['graph'] must be True, False, 'auto', 'host' or 'reuse'")
         self._graph_attempt = None
-        self._fusion = unused_kwargs.pop('fusion', 0)
+        fusion = unused_kwargs.pop('fusion', 0)
+        self._fusion = D.FUSION.get(fusion, fusion)
         _handle_unused_kwargs(self, unused_kwargs)
         self.func = func
         self.y0 = y0
@@ -763,43 +750,21 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
         self.ifactor = _convert_to_tensor(ifactor, dtype=np.float64)
         self.dfactor = _convert_to_tensor(dfactor, dtype=np.float64)
         self.max_num_steps = int(max_num_steps)
-        self._engine = None
         self._exchange = _Exchange(self._pg) if self._pg is not None else None
         self.stats = {}
 
+    def _options(self):
+        return dict(quartic=self.interp == N.INTERP_QUARTIC_MID, force_planes=self._force_planes, group=self._pg is not None, graph=self._graph)
+
+    def route(self):
+        """The engine this call is routed to (dispatch.Route), decided without running anything."""
+        return D.adaptive_rk(self.func, self.y0, len(self.tableau.alpha), _is_fsal_shaped(self.tableau), fusion=self._fusion, **self._options())
+
     # -- fused engine ----------------------------------------------------------------------------
-    def _make_engine(self):
-        rhs = None if self._force_planes else _fusable(self.func, self.y0)
-        from .rk_common import _is_fsal_shaped
-        one_row = len(self.tableau.alpha) == 1 and not _is_fsal_shaped(self.tableau)
-        if rhs is not None and one_row and hasattr(rhs, 'supports_coop'):
-            rhs = None                                       # adaptive_heun: the MLP tile kernels have no 1-row tableau - the cooperative kernel does
-        self._packed = None
-        if rhs is None and not self._force_planes and self._pg is None and self._fusion in (0, 'auto', 4, 'whole'):
-            rhs = _fusable_tuple(self.func, self.y0)            # tuple state of a row-local RHS: one segmented buffer
-            if rhs is not None:
-                self._packed = _pack_components(self.y0, rhs.dim)
-        self._coop = False
-        if rhs is None and not self._force_planes and self._pg is None and self._fusion in (0, 'auto', 4, 'whole') and len(self.y0) == 1:
-            # a network outside the tile kernels' box (float64, wide): the cooperative whole-call kernel, if the batch is co-resident there
-            cand = getattr(self.func, 'device_rhs', None)
-            y = self.y0[0]
-            if cand is not None and hasattr(cand, 'supports_coop') and isinstance(y, torch.Tensor) and y.is_cuda and y.numel() > 0 and \
-                    cand.supports_coop(y, any_box=one_row):
-                rhs, self._coop = cand, True
-            elif cand is not None and hasattr(cand, 'warn_limits') and isinstance(y, torch.Tensor) and y.is_cuda and not cand.coop_in_box(y):
-                cand.warn_limits(y)                                  # (e.g. hidden > 256: no kernel of the family takes it - said once)
-        if rhs is None:
-            return None
-        from .rk_common import _is_fsal_shaped
-        fsal, rows = _is_fsal_shaped(self.tableau), len(self.tableau.alpha)
-        if not (fsal and rows in (3, 6)) and not self._coop:           # (the cooperative kernel exists for every adaptive tableau)
-            # dopri8 (13 rows) and adaptive_heun (1 row, not FSAL shaped): row-local kernels only, no per-stage schedule
-            wide = (fsal and rows == 13) or (not fsal and rows == 1)
-            ok = getattr(rhs, 'row_local', False) or getattr(rhs, 'wide_tableaus', False) or \
-                (fsal and rows == 13 and getattr(rhs, 'tile_dopri8', False))
-            if not (wide and ok and self._fusion not in (1, 'stage')):
-                return None
+    def _make_engine(self, route):
+        """The engine of a fused route, or None where mi_ode_create has no kernel for this call after all: dispatch.after(route)."""
+        rhs = route.rhs
+        self._packed = _pack_components(self.y0, rhs.dim) if route.kind == 'fused_tuple' else None
         rtol0 = self.rtol if self.pooled_ratio else self.rtol[0]
         atol0 = self.atol if self.pooled_ratio else self.atol[0]
         first = None
@@ -817,7 +782,7 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
         key = ('adaptive', rhs.cache_key(y.dtype, y.device), tuple(y.shape), y.dtype, str(y.device),
                _tableau_key(self.tableau, self.c_mid), args, id(self._pg) if self._pg is not None else None,
                self._linear_variant, self._chunk_attempts, bool(self._profile), self._fusion, seg_rows, seg_tols)
-        if self._coop:                                           # (None: the batch's workgroups are not co-resident - remembered under the key)
+        if route.kind == 'fused_coop':                           # (None: the batch's workgroups are not co-resident - remembered under the key)
             eng = _cached_engine_or_none(key, lambda: _FusedEngine(
                 rhs, y, True, self.tableau, self.c_mid, *args, linear_variant=self._linear_variant, chunk_attempts=self._chunk_attempts,
                 profile=self._profile, fusion=self._fusion))
@@ -842,26 +807,34 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
 
     def integrate(self, t):
         _assert_increasing(t)
-        eng = self._make_engine()
-        if eng is not None and self._coop:
+        for y_ in self.y0:
+            N.require_gpu_tensor(y_, 'y0')
+        route = self.route()
+        out = self._integrate_on(route, t)
+        self.stats['route'] = route.kind                         # (as decided, whatever the run fell back to)
+        return out
+
+    def _integrate_on(self, route, t):
+        fused = route.kind in ('fused', 'fused_tuple', 'fused_coop')
+        eng = self._make_engine(route) if fused else None
+        if eng is not None and route.kind == 'fused_coop':
             # the cooperative kernel has the whole-call schedule only: no output beyond t[0], or a hand-off that timed out on a shared
             # GPU (nothing was committed) -> the device-controlled engine below
-            out = None
-            if len(t) > 1:
-                try:
-                    out = eng.integrate(t.to(torch.float64).numpy(), self.y0[0])
-                except SyncTimeout:
-                    out = None
+            try:
+                out = eng.integrate(t.to(torch.float64).numpy(), self.y0[0]) if len(t) > 1 else None
+            except SyncTimeout:
+                out = None
             if out is not None:
-                self.stats = eng.stats.as_dict()
-                self.stats['cross_rank'] = eng.transport
-                self.stats['engine'] = 'cooperative whole-call kernel (one launch, a thread per state element)'
+                self.stats = dict(eng.stats.as_dict(), cross_rank=eng.transport,
+                                  engine='cooperative whole-call kernel (one launch, a thread per state element)')
                 return (out,)
             eng = None
         if eng is None:
-            out = self._integrate_device_controlled(t)
-            if out is not None:
-                return out
+            host = D.after(route, D.device_controlled(self.y0, len(self.tableau.alpha), **self._options())) if fused else route
+            if host.told is not None:
+                host.told.warn_limits(self.y0[0])                # (e.g. hidden > 256: no kernel of the family takes it - said once)
+            if host.kind == 'callable':
+                return self._integrate_device_controlled(t)
             out = super(_AdaptiveRKSolver, self).integrate(t)
             self.stats = {'engine': 'plane kernels', 'n_attempts': getattr(self, '_n_attempts', 0),
                           'n_accepted': getattr(self, '_n_accepted', 0), 'status': 0}
@@ -884,20 +857,7 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
 
     # -- Python callable, controller on the device (graph_step.DeviceControlledRK) -----------------
     def _integrate_device_controlled(self, t):
-        """AdaptiveStepsizeODESolver.integrate (solvers.py:27-35) with the attempt loop's scalars on the device; None when this
-        problem has to take the host-controlled loop below (process group, mixed dtypes, an empty component, the 'host' option)."""
-        if self._graph == 'host' or self._force_planes or self._exchange is not None:
-            return None
-        y0 = self.y0
-        if not (1 <= len(y0) <= N.MAX_SEGMENTS) or len(self.tableau.alpha) + 1 not in (2, 4, 7, 14):
-            return None
-        like = y0[0]
-        if like.dtype not in (torch.float32, torch.float64):
-            return None
-        if any(y.dtype != like.dtype or y.device != like.device or y.numel() == 0 or not y.is_cuda for y in y0):
-            return None
-        if self.interp != N.INTERP_QUARTIC_MID and len(self.tableau.alpha) != 6:
-            return None
+        """AdaptiveStepsizeODESolver.integrate (solvers.py:27-35) with the attempt loop's scalars on the device: the 'callable' route."""
         from .graph_step import DeviceControlledRK, _credit_nfe, keep_recorded, recorded_engine
         t64 = t.to(torch.float64)                     # solvers.py:30
         self.before_integrate(t64)                    # f0 and the first step size, as the reference forms them (dopri5.py:70-79)
@@ -906,7 +866,7 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
         if eng is None:
             eng = DeviceControlledRK(self, graph=True if reuse else self._graph)
         try:
-            outs = eng.integrate(t64.numpy(), y0, self.rk_state.f1, float(self.rk_state.dt))
+            outs = eng.integrate(t64.numpy(), self.y0, self.rk_state.f1, float(self.rk_state.dt))
             st = eng.stats.as_dict()
             info = dict(eng.info)
             py_calls = eng.py_calls
@@ -937,8 +897,6 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
     def before_integrate(self, t):
         from .misc import _convert_to_tensor, _select_initial_step
         from .rk_common import _RungeKuttaState
-        for y_ in self.y0:
-            N.require_gpu_tensor(y_, 'y0')
         like = self.y0[0]
         t0 = float(t[0])
         if self.pooled_ratio:                                                     # tsit5.py:91-103
