@@ -4,8 +4,15 @@
 A "step" is one whole `odeint` call.  Default = config 4: linear f(t, y) = A y, dim 128, Dopri5,
 float64, rtol 1e-6, atol 1e-9, t = [0, 1]; inputs resident in HBM before the timed region.  ONE JSON line on stdout.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--config 1..5] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--config 1..5] [--dump-outputs DIR] [--full]
     python bench.py --config published [--published-all]     # the reference's own published workloads, one line each
+
+A plain run does only what the headline figure needs: set-up, the clock ramp, W warm-up steps, the K timed steps, the dump
+if asked for, the result line (with the `roofline` of the timed steps' own kernel, which costs no run of its own).  --full adds what
+takes runs of its own, all of it AFTER the timed steps, whose figures it therefore does not change: `cpu_baseline` with
+`parity_max_abs_diff` / `parity_attempts` (about 50 s of CPU work), `config.smi.sustained_loop` (1.5 s), `roofline_per_stage_schedule`
+(2 + 5 calls with the per-stage schedule) and, N > 1, `config.transport_survey`.  Without --full `cpu_baseline` is null and the
+other three are absent; `full` in the line says which kind of run it was.
 
 --dump-outputs DIR: after the timed steps, the solution the LAST timed step returned is written as DIR/solution.npy
 (DIR/solution_rank<r>.npy per rank when N > 1) in the step's own dtype, [len(t), rows, dim].  The files hold at most DUMP_MAX_BYTES (32 MiB) in all:
@@ -19,7 +26,7 @@ torch.distributed.run with N ranks, as a child process.  The line is refused (ex
   --scaling strong the fixed 65536 x 128 batch of BASELINE config 4 sharded N ways (N = 1: the same run as weak)
 The documented pair for a multi-GPU node is `--gpus N` (weak, what the driver runs) and `--gpus N --scaling strong`.
 N > 1 lines explain themselves: `config.per_rank[*].transport_log` = what every rank tried, in order, to carry the record and
-why each attempt ended as it did; `config.transport_survey` = every transport pinned in turn for 2 + 3 calls after the timed
+why each attempt ended as it did; `config.transport_survey` (--full) = every transport pinned in turn for 2 + 3 calls after the timed
 steps (ms_per_step each, or the reason it could not run; BENCH_NO_SURVEY=1 skips it).
 The batch shards by rows (trajectories are independent); the only exchange is one 6-double record per rank per step
 attempt (global error norm -> identical accept / dt decision on every rank); `config.cross_rank` names the
@@ -30,7 +37,7 @@ roofline:     the dominant kernel of the measured schedule; durations from HIP e
               libmi_ode (desc.profile), algorithmic bytes / flops per DESIGN.md section 4; `traffic` is the PMC figure of the
               committed rocprofv3 pass of this same command (profiles/*_summary.json; a counter pass cannot run inside
               the timed process), null if none is committed for the kernel.
-cpu_baseline: SURVEY.md 8(d): the op-for-op torch-CPU eager restatement of the reference path (oracle/ode_torch_cpu.py,
+cpu_baseline: (--full) SURVEY.md 8(d): the op-for-op torch-CPU eager restatement of the reference path (oracle/ode_torch_cpu.py,
               kind "port") on this host at the METRIC's configuration - the full 65536 x 128 shard - in worker processes whose
               threads are pinned (the parent restricts each worker to n CPUs on n distinct cores before exec, OMP_PROC_BIND=close; 8 = one CCD of this EPYC):
               8 threads 1 warm-up + up to 3 runs, 32 threads 1 + 2, 1 thread 1 + 1 (a 10 s budget per leg: one call takes 5 - 10 s
@@ -450,7 +457,11 @@ def main():
                     help="BASELINE.json configuration (default: the headline, 4); 'published': the workloads the reference publishes wall times "
                          "for (examples/ode_usage.ipynb, lorenz_attractor.py), as the Python callables it writes them")
     ap.add_argument('--published-all', action='store_true', help='--config published: every system of the notebook, not only the ones BASELINE.md lists')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own, after the timed steps: the CPU baseline and the parity check against the '
+                         'oracle, the sustained loop with the board telemetry, the per-stage schedule\'s roofline and, N > 1, the transport '
+                         'survey (see the module docstring); off by default')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without its CPU baseline / parity leg (a plain run has none)')
     ap.add_argument('--cpu-worker', type=int, default=0, help='internal: run the pinned torch-CPU leg with this many threads and exit')
     ap.add_argument('--cpu-runs', type=int, default=3)
     ap.add_argument('--linear-variant', type=int, default=0)
@@ -625,7 +636,7 @@ def main():
                                           'transport_log': stats.get('cross_rank_log')})
     # The same call in a loop for 1.5 s with the files sampled every 10 ms, OUTSIDE the timed region (after it): power against its cap,
     # the clock the driver reports and the temperatures while the kernel of the timed steps is all the part does.
-    if len(hw.dirs) > 0 and os.environ.get('BENCH_NO_SMI_LOOP') != '1':
+    if args.full and len(hw.dirs) > 0 and os.environ.get('BENCH_NO_SMI_LOOP') != '1':
         clk2 = []
 
         def _one():
@@ -637,7 +648,7 @@ def main():
         if use_dist:
             dist.barrier()
     survey = None
-    if use_dist and args.config == 4 and args.transport == 'auto' and os.environ.get('BENCH_NO_SURVEY') != '1':
+    if args.full and use_dist and args.config == 4 and args.transport == 'auto' and os.environ.get('BENCH_NO_SURVEY') != '1':
         # First contact with a multi-GPU node should explain itself: OUTSIDE the timed region, every transport in turn (pinned, so
         # nothing falls through silently) runs 2 + 3 calls; the line then carries what each one did - or why it could not run -
         # next to the one the timed steps used.  Collective-safe: every rank walks the same list.
@@ -699,7 +710,7 @@ def main():
                'clock_mhz': (clk_sum / clk_n) if clk_n else None,
                'handoff_us': stats.get('handoff_us'),           # workgroup 0's time in the grid hand-offs of the last timed call
                # what the driver reports beside it (class Hwmon): a reading right before and right after the timed steps, and the same call
-               # in a 1.5 s loop afterwards with power / sclk / temperatures sampled every 10 ms
+               # (--full) in a 1.5 s loop afterwards with power / sclk / temperatures sampled every 10 ms
                'smi': smi}
         if per_rank is not None:
             cfg['per_rank'] = per_rank
@@ -758,7 +769,7 @@ def main():
                         'traffic': traffic, 'traffic_source': src,
                         'kernel': 'k_stage_linear_mfma<double,128,6,LAST_FSAL> (Dopri5 stage 6 + error norms)',
                         'algorithmic_bytes_per_launch': bytes_last, 'avg_launch_ms': last_ms, 'launches_timed': prof_n}
-            if step_fused and n_gpus == 1 and not use_dist:
+            if args.full and step_fused and n_gpus == 1 and not use_dist:
                 # The north star names the per-stage structure's fused "stage + error" kernel and an HBM target (>= 60 %).
                 # The default schedule above replaced it (it is 1.8x faster end to end); measure that kernel too, OUTSIDE
                 # the timed region, so one bench line carries both rooflines.
@@ -824,7 +835,7 @@ def main():
             'metric': 'state-elements/sec (batch x dim / wall-s) %s' % ('Dopri5 float64' if args.config == 4 else 'config %d' % args.config),
             'value': value, 'unit': 'state-elements/s', 'n_gpus': n_gpus, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
-            'dtype': dtype_name, 'data': 'synthetic', 'config': cfg, 'roofline': roof,
+            'dtype': dtype_name, 'data': 'synthetic', 'full': bool(args.full), 'config': cfg, 'roofline': roof,
         }
         if stage_roof is not None:
             res['roofline_per_stage_schedule'] = stage_roof
@@ -839,7 +850,7 @@ def main():
             roof['granted_clock_mhz'] = clk
             roof['frac_at_granted_clock'] = roof['frac'] * NOMINAL_CLOCK_MHZ / clk
         res['cpu_baseline'] = None
-        if not args.no_cpu_baseline and n_gpus == 1 and args.config == 4 and args.batch == BATCH:
+        if args.full and not args.no_cpu_baseline and n_gpus == 1 and args.config == 4 and args.batch == BATCH:
             res['cpu_baseline'], res['parity_max_abs_diff'], ref_attempts = cpu_baseline(out)
             res['parity_attempts'] = {'gpu': attempts, 'oracle': ref_attempts}
         sys.stdout.flush()

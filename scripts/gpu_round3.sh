@@ -16,7 +16,7 @@ tests)
   timeout 2400 python -m pytest tests -m gpu -q -x -rs 2>&1 | tail -30 | tee gpurun_out/r03_pytest_gpu.txt
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 ;;
 bench)
-  python bench.py > gpurun_out/r03_bench_config4.json 2> gpurun_out/r03_bench_config4.err; cut -c1-400 gpurun_out/r03_bench_config4.json
+  python bench.py --full > $TMPDIR/r03_bench_config4.json 2> $TMPDIR/r03_bench_config4.err; cut -c1-400 $TMPDIR/r03_bench_config4.json
   for c in 1 2 3 5; do python bench.py --config $c --no-cpu-baseline 2>/dev/null | tee -a gpurun_out/r03_bench_other_configs.jsonl | cut -c1-240; done ;;
 profiles)
   P=gpurun_out/profiles_r03; rm -rf $P; mkdir -p $P

@@ -28,14 +28,14 @@ first)
   done ;;
 second)
   timeout 2400 python -m pytest tests -m gpu -q -rs 2>&1 | tail -60 | tee gpurun_out/r04_pytest_gpu.txt
-  python bench.py > gpurun_out/r04_bench_config4.json 2> gpurun_out/r04_bench_config4.err; cut -c1-1500 gpurun_out/r04_bench_config4.json; tail -3 gpurun_out/r04_bench_config4.err
+  python bench.py --full > $TMPDIR/r04_bench_config4.json 2> $TMPDIR/r04_bench_config4.err; cut -c1-1500 $TMPDIR/r04_bench_config4.json; tail -3 $TMPDIR/r04_bench_config4.err
   TFDIFFEQ_AMD_LIB=$V/libmi_ode_prof.so python bench.py --no-cpu-baseline > gpurun_out/r04_bench_prof.json 2> gpurun_out/r04_bench_prof.err
   echo "== variant prof"; cut -c1-200 gpurun_out/r04_bench_prof.json; grep "persist" gpurun_out/r04_bench_prof.err | tail -9 ;;
 tests)
   timeout 2400 python -m pytest tests -m gpu -q -rfs --tb=short > gpurun_out/r04_pytest_gpu_full.txt 2>&1; grep -E "^(FAILED|ERROR)|passed|failed" gpurun_out/r04_pytest_gpu_full.txt | cut -c1-260 | tail -60
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 ;;
 bench)
-  python bench.py > gpurun_out/r04_bench_config4.json 2> gpurun_out/r04_bench_config4.err; cut -c1-400 gpurun_out/r04_bench_config4.json
+  python bench.py --full > $TMPDIR/r04_bench_config4.json 2> $TMPDIR/r04_bench_config4.err; cut -c1-400 $TMPDIR/r04_bench_config4.json
   for c in 1 2 3 5; do python bench.py --config $c --no-cpu-baseline 2>/dev/null | tee -a gpurun_out/r04_bench_other_configs.jsonl | cut -c1-240; done ;;
 profiles)
   P=gpurun_out/profiles_r04; rm -rf $P; mkdir -p $P

@@ -15,7 +15,7 @@ tests)
   timeout 2700 python -m pytest tests -m gpu -q -rfs --tb=short > gpurun_out/r05_pytest_gpu_full.txt 2>&1; grep -E "^(FAILED|ERROR)|passed|failed" gpurun_out/r05_pytest_gpu_full.txt | cut -c1-260 | tail -60
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 ;;
 bench)
-  python bench.py > $P/r05_bench_config4.json 2> gpurun_out/r05_bench_config4.err; cut -c1-600 $P/r05_bench_config4.json; tail -2 gpurun_out/r05_bench_config4.err
+  python bench.py --full > $P/r05_bench_config4.json 2> $TMPDIR/r05_bench_config4.err; cut -c1-600 $P/r05_bench_config4.json; tail -2 $TMPDIR/r05_bench_config4.err
   rm -f $P/r05_bench_other_configs.jsonl
   for c in 1 2 3 5; do python bench.py --config $c --no-cpu-baseline 2>/dev/null | tee -a $P/r05_bench_other_configs.jsonl | cut -c1-240; done ;;
 power)

@@ -13,7 +13,7 @@ if want tests; then
   tail -3 $O/r06_pytest_gpu_summary.txt
 fi
 if want bench; then
-  timeout 600 python bench.py > $O/r06_bench_config4.json 2> $O/r06_bench_config4.err; tail -c 600 $O/r06_bench_config4.json
+  timeout 600 python bench.py --full > $O/r06_bench_config4.json 2> $O/r06_bench_config4.err; tail -c 600 $O/r06_bench_config4.json
   timeout 300 python bench.py --config 5 --no-cpu-baseline > $O/r06_bench_config5.json 2>/dev/null
 fi
 if want published; then

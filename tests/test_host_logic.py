@@ -390,6 +390,33 @@ def test_bench_refuses_more_ranks_than_devices_with_one_line():
     assert len(lines) == 1 and '--gpus 2' in lines[0] and 'device(s) visible' in lines[0]
 
 
+def test_bench_full_is_an_option_that_is_off_by_default():
+    """`bench.py --full` exists and is off by default, and every measurement that takes runs of its own (the CPU baseline, the sustained
+    loop, the per-stage schedule's roofline, the transport survey) sits behind it in main()."""
+    import ast
+    import subprocess
+    import sys
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0 and '--full' in res.stdout
+    tree = ast.parse(open(os.path.join(ROOT, 'bench.py')).read())
+    main = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == 'main'][0]
+    full = [n for n in ast.walk(main) if isinstance(n, ast.Call) and getattr(n.func, 'attr', '') == 'add_argument'
+            and n.args and getattr(n.args[0], 'value', None) == '--full'][0]
+    assert any(k.arg == 'action' and k.value.value == 'store_true' for k in full.keywords)
+
+    def guarded(marker):
+        """the test of the innermost `if` whose body holds the line that contains `marker`"""
+        best = None
+        for n in ast.walk(main):
+            if isinstance(n, ast.If) and any(marker in ast.unparse(b) for b in n.body):
+                if best is None or (n.lineno >= best.lineno and n.end_lineno <= best.end_lineno):
+                    best = n
+        assert best is not None, marker
+        return ast.unparse(best.test)
+    for marker in ('cpu_baseline(out)', 'hw.sample_while(', "fusion='stage'", "('peer', 'host', 'rccl', 'hook')"):
+        assert 'args.full' in guarded(marker), marker
+
+
 def test_bench_dump_outputs_is_a_fixed_sample_within_the_budget(tmp_path, monkeypatch):
     """`bench.py --dump-outputs`: a solution over the byte budget is cut to the same sorted, seeded rows on every call (two builds compare
     file for file), every output time and component kept; a small one is written whole; N ranks share the budget."""
