@@ -231,7 +231,8 @@ const char* mi_ode_status_string(uint32_t status_bits);   /* reference assertion
 const char* mi_ode_last_error(void);                      /* thread-local text of the last negative return */
 int64_t mi_ode_reduce_workspace_bytes(void);              /* scratch the stateless reductions need */
 int64_t mi_ode_sizeof(int32_t which);                     /* 0: mi_ode_desc, 1: mi_ode_stats, 2: mi_ode_tableau, 3: mi_ode_rhs,
-                                                             5: mi_ode_ctrl_params, 6: mi_ode_adjoint_desc, 7: mi_ode_opq_desc, 8: mi_ode_linadj_desc
+                                                             5: mi_ode_ctrl_params, 6: mi_ode_adjoint_desc, 7: mi_ode_opq_desc, 8: mi_ode_linadj_desc,
+                                                             9: mi_ode_discrete_desc
                                                              (lets a foreign-language binding verify its struct layout) */
 
 /* ---- (A) fused engine ---------------------------------------------------------------------- */
@@ -395,6 +396,31 @@ int mi_ode_linadj_segment(mi_ode_linadj_handle h, const void* w_dev, const void*
 /* where the time of the last segment went, microseconds of workgroup 0: {tile passes, adj_params combinations, hand-offs of the
  * attempts, slab passes, folds + small products with their hand-offs, prologue, epilogue, hand-offs (count)} */
 int mi_ode_linadj_profile(mi_ode_linadj_handle h, double* out8);
+
+/* ---- (A'''') exact gradient of a fixed-grid solve: the reverse sweep of the discrete map, ONE launch --------------------- */
+/* The reference trains by back-propagating through the solver's own ops (tfdiffeq/fixed_grid.py under the caller's tape); what that
+ * returns is the gradient of the discrete map y_{n+1} = y_n + h sum_i b_i f(Y_i), not the continuous adjoint's.  This entry point is that
+ * gradient for the time-independent ODEFunc MLP (MI_ODE_RHS_MLP_TANH, fp32, state [batch, dim]) on the default grid (the output times
+ * are the grid): with lambda_{n+1} the gradient at y_{n+1}, for i = s .. 1
+ *     kbar_i = h b_i lambda_{n+1} + h sum_{j>i} a_ji Ybar_j,   Ybar_i = (df/dy at Y_i)^T kbar_i,   theta_bar += (df/dtheta at Y_i)^T kbar_i,
+ * lambda_n = lambda_{n+1} + sum_i Ybar_i + (the output gradient at grid point n).  The stages are recomputed from the stored y_n. */
+typedef struct mi_ode_discrete_desc {
+  int64_t batch;
+  int32_t dim, hidden;
+  mi_ode_tableau tableau;     /* explicit, at most 3 rows (4 stages): beta = a_ij, c_sol = b (euler: no rows; midpoint, heun: one; rk4: three) */
+  int32_t n_points;           /* grid points N (N - 1 steps), 2 <= N <= 1025 */
+  int32_t chunk_tiles;        /* 32-row tiles of a workgroup that share one weight-gradient pass; 0: all of them */
+} mi_ode_discrete_desc;
+typedef struct mi_ode_discrete* mi_ode_discrete_handle;
+int mi_ode_discrete_create(const mi_ode_discrete_desc* desc, mi_ode_discrete_handle* out);
+int mi_ode_discrete_destroy(mi_ode_discrete_handle h);
+int64_t mi_ode_discrete_num_params(mi_ode_discrete_handle h);
+/* t_host: the N grid times (host).  ys_dev: the forward solution [N, batch, dim]; grad_ys_dev: the gradient of the loss with respect
+ * to it, same shape; grad_y0_out_dev [batch, dim]; grad_theta_out_dev: mi_ode_discrete_num_params() entries in the canonical order of
+ * (A').  All device memory, fp32.  rhs: the weights (sign is ignored).  Deterministic: two calls give identical bits.  Blocks until
+ * done; returns status bits (>= 0) or an error (< 0).  stats->n_launches == 1. */
+int mi_ode_discrete_sweep(mi_ode_discrete_handle h, const mi_ode_rhs* rhs, const double* t_host, const void* ys_dev,
+                          const void* grad_ys_dev, void* grad_y0_out_dev, void* grad_theta_out_dev, mi_ode_stats* stats, void* stream);
 
 /* ---- function-level parity surface of the step controller ----------------------------------- */
 /* The scalar tail of one step attempt exactly as the kernels run it (csrc/mi_ode_ctrl_dev.h, ONE device thread per case):

@@ -1,0 +1,122 @@
+"""A full training step (forward + loss + backward) with the gradient of the discrete map, three ways, at config 5's shape (64-128-128-64
+tanh, float32, batch 32768) and at batch 4096, for rk4 on 5 and 21 grid points and one-step Euler:
+
+  taped    the solver loop written in torch ops and back-propagated - what a user has to write without odeint_discrete
+           (tests/discrete_restatement.py);
+  generic  ODEBlock(gradient='discrete') with the generic sweep (discrete.FUSED = False): fused forward, one taped step + one
+           torch.autograd.grad call per grid interval backward;
+  fused    ODEBlock(gradient='discrete'): fused forward, the whole backward in one launch (csrc/mi_ode_discrete.h).
+
+One process, in-run HIP events, min / median / max over the timed steps after the warm-up.  The fused kernel alone is timed too; its
+fraction of the fp32 matrix peak (157.3 TFLOP/s) follows from its own multiply-add count: forward recompute, backward data and weight
+gradients, 3 x (d h + h h + h d) per row, stage and step.
+
+usage: python scripts/bench_discrete.py [--steps 20] [--warmup 5] [--chunks 0,1] [--out profiles/discrete_bench.txt] [--only fused]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from tfdiffeq_amd import discrete, models, odeint_discrete  # noqa: E402
+from tests import discrete_restatement as DR  # noqa: E402
+
+PEAK = 157.3e12
+DIM, HID = 64, 128
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return min(ms), statistics.median(ms), max(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--chunks', default='0,1', help='tiles per weight-gradient pass of the fused kernel to compare (0: all of a workgroup\'s)')
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'discrete_bench.txt'))
+    ap.add_argument('--only', default='', help='comma-separated subset of taped,generic,fused')
+    args = ap.parse_args()
+    only = set(filter(None, args.only.split(',')))
+    dev = torch.device('cuda:0')
+    lines = ['# scripts/bench_discrete.py --steps %d --warmup %d: %s, 64-128-128-64 tanh float32; ms per training step (min / median / max)'
+             % (args.steps, args.warmup, torch.cuda.get_device_name(0))]
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    for batch in (32768, 4096):
+        torch.manual_seed(0)
+        func = models.ODEFunc(DIM, HID, non_linearity='tanh').to(dev)
+        x = torch.randn(batch, DIM, device=dev)
+        w = torch.randn(batch, DIM, device=dev)
+        for method, n in (('rk4', 5), ('rk4', 21), ('euler', 2)):
+            t = torch.linspace(0., 1., n)
+            block = models.ODEBlock(func, solver=method, gradient='discrete')
+
+            def zero():
+                for p in func.parameters():
+                    p.grad = None
+
+            def taped():
+                zero()
+                xi = x.clone().requires_grad_(True)
+                (DR.solve(func, xi, t, method)[-1] * w).sum().backward()
+
+            def block_step():
+                zero()
+                xi = x.clone().requires_grad_(True)
+                (block(xi, eval_times=t)[-1] * w).sum().backward()
+
+            head = 'batch %5d %-5s N=%2d' % (batch, method, n)
+            if not only or 'taped' in only:
+                say('%s  taped torch loop      %9.3f / %9.3f / %9.3f' % ((head,) + timed(taped, args.steps, args.warmup)))
+            if not only or 'generic' in only:
+                discrete.FUSED = False
+                res = timed(block_step, args.steps, args.warmup)
+                assert odeint_discrete.last_backward_stats['engine'] == 'generic sweep'
+                say('%s  generic sweep         %9.3f / %9.3f / %9.3f' % ((head,) + res))
+            if only and 'fused' not in only:
+                continue
+            discrete.FUSED = True
+            for chunk in [int(c) for c in args.chunks.split(',')]:
+                discrete.CHUNK_TILES = chunk
+                res = timed(block_step, args.steps, args.warmup)
+                st = odeint_discrete.last_backward_stats
+                assert st['engine'] == 'fused mlp sweep' and st['n_launches'] == 1, st
+                # the kernel alone: the engine's blocking sweep call on the last forward solution
+                eng = discrete._cached_engine(batch, DIM, HID, method, n, str(dev), chunk)
+                with torch.no_grad():
+                    ys = block(x, eval_times=t).contiguous()
+                gys = torch.zeros_like(ys)
+                gys[-1] = w
+                tt = t.double().numpy()
+                mlp = func.device_rhs()
+                k = timed(lambda: eng.sweep(mlp, tt, ys, gys), args.steps, args.warmup)
+                mac = batch * (n - 1) * DR.STAGES[method] * 3 * (DIM * HID + HID * HID + HID * DIM)
+                say('%s  fused sweep chunk=%-3d %9.3f / %9.3f / %9.3f   kernel alone %8.3f / %8.3f / %8.3f ms = %.1f %% of the fp32 matrix peak (median)'
+                    % ((head, chunk) + res + k + (100.0 * 2 * mac / (k[1] * 1e-3) / PEAK,)))
+            discrete.CHUNK_TILES = 0
+    with open(args.out, 'w') as f:
+        f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()

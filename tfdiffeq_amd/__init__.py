@@ -7,11 +7,12 @@ See DESIGN.md for the path, its boundary and the kernels; INTEGRATION.md for the
 """
 from .odeint import odeint, SOLVERS
 from .adjoint import odeint_adjoint
+from .discrete import odeint_discrete
 from .misc import move_to_device
 from . import rhs
 from . import hyper_solvers
 from .solvers import clear_engine_cache
 
-__all__ = ['odeint', 'odeint_adjoint', 'SOLVERS', 'move_to_device', 'rhs', 'clear_engine_cache']
+__all__ = ['odeint', 'odeint_adjoint', 'odeint_discrete', 'SOLVERS', 'move_to_device', 'rhs', 'clear_engine_cache']
 
 __version__ = '0.1.0'

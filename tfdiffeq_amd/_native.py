@@ -91,6 +91,12 @@ class LinAdjDesc(C.Structure):
                 ('order', C.c_int32), ('init_order', C.c_int32), ('max_num_steps', C.c_int64)]
 
 
+class DiscreteDesc(C.Structure):
+    """mi_ode_discrete_desc: the reverse sweep of a fixed-grid solve of the ODEFunc MLP in one launch (exact gradient of the discrete map)."""
+    _fields_ = [('batch', C.c_int64), ('dim', C.c_int32), ('hidden', C.c_int32), ('tableau', Tableau),
+                ('n_points', C.c_int32), ('chunk_tiles', C.c_int32)]
+
+
 class OpqDesc(C.Structure):
     """mi_ode_opq_desc: adaptive RK over an opaque (Python) right-hand side with the controller on the device."""
     _fields_ = [('dtype', C.c_int32), ('n_comp', C.c_int32), ('n', C.c_int64 * MAX_SEGMENTS), ('tableau', Tableau),
@@ -190,6 +196,11 @@ _PROTOS = {
     'mi_ode_linadj_segment': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                         C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(Stats), C.c_void_p]),
     'mi_ode_linadj_profile': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    'mi_ode_discrete_create': (C.c_int, [C.POINTER(DiscreteDesc), C.POINTER(C.c_void_p)]),
+    'mi_ode_discrete_destroy': (C.c_int, [C.c_void_p]),
+    'mi_ode_discrete_num_params': (C.c_int64, [C.c_void_p]),
+    'mi_ode_discrete_sweep': (C.c_int, [C.c_void_p, C.POINTER(Rhs), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(Stats), C.c_void_p]),
     'mi_ode_opq_create': (C.c_int, [C.POINTER(OpqDesc), C.POINTER(C.c_void_p)]),
     'mi_ode_opq_destroy': (C.c_int, [C.c_void_p]),
     'mi_ode_opq_dt_dev': (C.c_void_p, [C.c_void_p]),
@@ -272,7 +283,7 @@ def load():
         fn.argtypes = args
     if lib.mi_ode_abi_version() != ABI_VERSION:
         raise NativeError('libmi_ode.so ABI version mismatch')
-    for which, st in ((0, Desc), (1, Stats), (2, Tableau), (3, Rhs), (5, CtrlParams), (6, AdjointDesc), (7, OpqDesc), (8, LinAdjDesc)):
+    for which, st in ((0, Desc), (1, Stats), (2, Tableau), (3, Rhs), (5, CtrlParams), (6, AdjointDesc), (7, OpqDesc), (8, LinAdjDesc), (9, DiscreteDesc)):
         if lib.mi_ode_sizeof(which) != C.sizeof(st):
             raise NativeError('struct layout mismatch for %s: C %d vs ctypes %d'
                               % (st.__name__, lib.mi_ode_sizeof(which), C.sizeof(st)))

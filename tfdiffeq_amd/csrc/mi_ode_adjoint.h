@@ -353,6 +353,9 @@ struct AdjWList {              // one weight-gradient pass: activation slots and
   int slot[8];
   float c[2][8];
   float ts[8];                 // the time the network saw at that slot's stage (time-dependent network: the gradient of w_t)
+  // SWEEP instantiation of the pass only (csrc/mi_ode_discrete.h): the pass covers ntile tiles of the workgroup, whose activations sit at
+  // scratch items blockIdx.x * cap + 0 .. ntile - 1 with 4 slots each; accum: add to the partials already there
+  int ntile, cap, accum;
 };
 
 struct AdjShared {
@@ -529,7 +532,7 @@ __device__ __forceinline__ float adj_load_agent(const g_float* p) { return __hip
 // sum over this workgroup's tiles and the listed activation slots of  coef * X^T Delta  for the three layers (+ column
 // sums for the biases), NC coefficient sets at once; the result goes to this workgroup's block of A.wpart, combinations
 // c_base .. c_base + NC - 1, canonical parameter order.  The list is ash->wl[list].
-template <int DP, int HP, int NC>
+template <int DP, int HP, int NC, bool SWEEP = false>
 __device__ __attribute__((noinline)) void adj_wgrad_pass(const AdjArgs* A_, unsigned smem, unsigned ash_off, int list, int c_base) {
   using G = AdjGeom<DP, HP>;
   constexpr int CB = G::CB, HB = G::HB;
@@ -565,11 +568,14 @@ __device__ __attribute__((noinline)) void adj_wgrad_pass(const AdjArgs* A_, unsi
   const long long ntiles = (A.p.s.batch + G::R - 1) / G::R;
   const int colw = 16 * w + li;                             // this lane's column inside the wave's 16-column block
   const int nlist = uniform_i(L.n);
-  const long long my_tiles = (long long)blockIdx.x < ntiles ? (ntiles - 1 - blockIdx.x) / gridDim.x + 1 : 0;
+  const long long my_tiles = SWEEP ? (long long)uniform_i(L.ntile) : ((long long)blockIdx.x < ntiles ? (ntiles - 1 - blockIdx.x) / gridDim.x + 1 : 0);
   const int nsteps = (int)(my_tiles * nlist * 2);           // (tile, listed slot, half) in this order
   const g_float* const act_base = (const g_float*)A.act;
+  const long long sweep_item0 = SWEEP ? (long long)blockIdx.x * uniform_i(L.cap) : 0;
+  const bool accum = SWEEP && uniform_i(L.accum) != 0;
   auto step_ptr = [&](int step) -> const g_float* {         // + 4 half: MFMA k slot lg of sub-step j <-> tile row 8 lg + 4 half + j
     const int half = step & 1, q = (step >> 1) % nlist;
+    if (SWEEP) return act_base + ((sweep_item0 + (step >> 1) / nlist) * 4 + uniform_i(L.slot[q])) * (long long)G::SLOT + 4 * half;
     const long long tile_i = blockIdx.x + (long long)((step >> 1) / nlist) * gridDim.x;
     return act_base + (tile_i * G::NSLOT + uniform_i(L.slot[q])) * (long long)G::SLOT + 4 * half;
   };
@@ -685,40 +691,42 @@ __device__ __attribute__((noinline)) void adj_wgrad_pass(const AdjArgs* A_, unsi
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       g_float* out = (g_float*)A.wpart + ((long long)blockIdx.x * 3 + c_base + c) * A.Ppad;
+      // (SWEEP: this workgroup's own partial of the earlier passes of the launch - written through, read back at the same scope)
+      auto put = [&](g_float* p, float v) { adj_store_agent(p, accum ? adj_load_agent(p) + v : v); };
       // accumulator element i of block (mb, nb): row m = 16 mb + 4 lg + i (input unit), column n = 16 nb + li (output unit)
 #pragma unroll
       for (int b = 0; b < CB; ++b)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int m = 16 * b + 4 * lg + i;
-          if (m < d && colw < hd) adj_store_agent(out + (unsigned)(oW1 + m * hd + colw), g1[c][b][i]);
+          if (m < d && colw < hd) put(out + (unsigned)(oW1 + m * hd + colw), g1[c][b][i]);
         }
 #pragma unroll
       for (int b = 0; b < HB; ++b)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int m = 16 * b + 4 * lg + i;
-          if (m < hd && colw < hd) adj_store_agent(out + (unsigned)(oW2 + m * hd + colw), g2[c][b][i]);
+          if (m < hd && colw < hd) put(out + (unsigned)(oW2 + m * hd + colw), g2[c][b][i]);
         }
 #pragma unroll
       for (int b = 0; b < CB; ++b)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int m = 16 * w + 4 * lg + i, n = 16 * b + li;
-          if (m < hd && n < d) adj_store_agent(out + (unsigned)(oW3 + m * d + n), g3[c][b][i]);
+          if (m < hd && n < d) put(out + (unsigned)(oW3 + m * d + n), g3[c][b][i]);
         }
       // bias gradients: a lane summed rows 8 lg .. 8 lg + 7 of every tile; fold the four lane groups
       float t1 = s1[c], t2 = s2[c], tt = st[c];
       t1 += __shfl_xor(t1, 16, 64); t1 += __shfl_xor(t1, 32, 64);
       t2 += __shfl_xor(t2, 16, 64); t2 += __shfl_xor(t2, 32, 64);
       tt += __shfl_xor(tt, 16, 64); tt += __shfl_xor(tt, 32, 64);
-      if (lg == 0 && colw < hd) { adj_store_agent(out + (unsigned)(oB1 + colw), t1); adj_store_agent(out + (unsigned)(oB2 + colw), t2); }
-      if (td && lg == 0 && colw < hd) adj_store_agent(out + (unsigned)colw, tt);
+      if (lg == 0 && colw < hd) { put(out + (unsigned)(oB1 + colw), t1); put(out + (unsigned)(oB2 + colw), t2); }
+      if (td && lg == 0 && colw < hd) put(out + (unsigned)colw, tt);
 #pragma unroll
       for (int b = 0; b < CB; ++b) {
         float t3 = s3[c][b];
         t3 += __shfl_xor(t3, 16, 64); t3 += __shfl_xor(t3, 32, 64);
-        if (w == 0 && lg == 0 && 16 * b + li < d) adj_store_agent(out + (unsigned)(oB3 + 16 * b + li), t3);
+        if (w == 0 && lg == 0 && 16 * b + li < d) put(out + (unsigned)(oB3 + 16 * b + li), t3);
       }
     }
   }

@@ -12,6 +12,7 @@ from torch import nn
 from . import dispatch as _dispatch
 from . import rhs as _rhs
 from .adjoint import odeint_adjoint
+from .discrete import TABLEAUS as _DISCRETE_METHODS, odeint_discrete
 from .odeint import odeint
 
 MAX_NUM_STEPS = 1000          # dense_odenet.py:14
@@ -105,8 +106,16 @@ class LinearODEFunc(nn.Module):
 class ODEBlock(nn.Module):
     """Solves the ODE defined by odefunc (dense_odenet.py:95-191)."""
 
-    def __init__(self, odefunc, is_conv=False, tol=1e-3, adjoint=False, solver='dopri5'):
+    def __init__(self, odefunc, is_conv=False, tol=1e-3, adjoint=False, solver='dopri5', gradient='adjoint'):
         super(ODEBlock, self).__init__()
+        # gradient: 'adjoint' (default) - the continuous adjoint solve; 'discrete' - the gradient of the discrete map the fixed-grid
+        # solver computed, what back-propagating through the reference's solver gives (discrete.odeint_discrete)
+        if gradient not in ('adjoint', 'discrete'):
+            raise ValueError("gradient must be 'adjoint' or 'discrete', not %r" % (gradient,))
+        if gradient == 'discrete' and solver not in _DISCRETE_METHODS:
+            raise ValueError("gradient='discrete' is the gradient of a fixed-grid solver's discrete map: solver must be one of %s, not %r "
+                             "(use gradient='adjoint' with adaptive and multistep solvers)" % (sorted(_DISCRETE_METHODS), solver))
+        self.gradient = gradient
         self.is_conv = is_conv
         self.adjoint = adjoint
         self.odefunc = odefunc
@@ -133,24 +142,20 @@ class ODEBlock(nn.Module):
             x_aug = x
         needs_grad = torch.is_grad_enabled() and (x_aug.requires_grad or any(p.requires_grad for p in self.odefunc.parameters()))
         kw = dict(rtol=self.tol, atol=self.tol, method=self.method, options=self.options)
-        if needs_grad:
+        if needs_grad and self.gradient == 'discrete':
+            # the forward solve as the inference branch below runs it (the fused kernels where the network has them), the backward as the
+            # transpose of that discrete map
+            func, fused = self._inference_func(x_aug)
+            out = odeint_discrete(self.odefunc, x_aug, integration_time, method=self.method, options=self.options, _forward_func=func)
+            if func is fused:
+                self.odefunc.nfe += int(odeint.last_stats.get('nfe', 0))
+        elif needs_grad:
             # adjoint=True: the reference's odeint_adjoint branch (:178-181).  adjoint=False: the reference differentiates
             # through the solver's ops; the kernels here are not taped, so the gradient is obtained from the adjoint
             # solve in that case too (same gradient up to the solver tolerance) - never silently dropped.
             out = odeint_adjoint(self.odefunc, x_aug, integration_time, **kw)
         else:
-            fused = None if needs_grad else self.odefunc.device_rhs()
-            if self.is_conv:
-                # rhs.Conv2dODE: the fused stage kernel where it takes the shape and is the faster route (larger shapes run the torch
-                # module, rhs.Conv2dODE.FUSED_MAX_CONV2_FLOP); outside its box the descriptor says why, once
-                why = fused.in_box(x_aug) if x_aug.is_cuda else 'a host tensor'
-                if why and x_aug.is_cuda:
-                    fused.warn_limits(x_aug, why)
-                func = fused if (not why and fused.faster_than_torch(x_aug)) else self.odefunc
-            else:
-                # (the tile kernels, or - float64 / wider networks, round 5 - the cooperative one-launch kernel; if neither takes the problem
-                # the solver runs the descriptor's own forward() as a callable on the device-controlled engine and says so once)
-                func = fused if (fused is not None and _dispatch.has_kernel(fused, x_aug)) else self.odefunc
+            func, fused = self._inference_func(x_aug)
             with torch.no_grad():
                 out = odeint(func, x_aug, integration_time, **kw)                           # :184-186
             if func is fused:                                    # f ran inside the kernel: the counter the reference exposes
@@ -158,6 +163,22 @@ class ODEBlock(nn.Module):
         if eval_times is None:
             return out[1]                                        # :188-189
         return out
+
+    def _inference_func(self, x_aug):
+        """(what an untaped forward solve hands to odeint, the network's fused descriptor or None)."""
+        fused = self.odefunc.device_rhs()
+        if self.is_conv:
+            # rhs.Conv2dODE: the fused stage kernel where it takes the shape and is the faster route (larger shapes run the torch
+            # module, rhs.Conv2dODE.FUSED_MAX_CONV2_FLOP); outside its box the descriptor says why, once
+            why = fused.in_box(x_aug) if x_aug.is_cuda else 'a host tensor'
+            if why and x_aug.is_cuda:
+                fused.warn_limits(x_aug, why)
+            func = fused if (not why and fused.faster_than_torch(x_aug)) else self.odefunc
+        else:
+            # (the tile kernels, or - float64 / wider networks, round 5 - the cooperative one-launch kernel; if neither takes the problem
+            # the solver runs the descriptor's own forward() as a callable on the device-controlled engine and says so once)
+            func = fused if (fused is not None and _dispatch.has_kernel(fused, x_aug)) else self.odefunc
+        return func, fused
 
     def trajectory(self, x, timesteps):
         """dense_odenet.py:193-205."""
@@ -171,12 +192,12 @@ class ODENet(nn.Module):
     """An ODEBlock followed by a linear layer (dense_odenet.py:208-259)."""
 
     def __init__(self, input_dim, hidden_dim, output_dim, augment_dim=0, time_dependent=False, non_linearity='relu',
-                 tol=1e-3, adjoint=False, solver='dopri5'):
+                 tol=1e-3, adjoint=False, solver='dopri5', gradient='adjoint'):
         super(ODENet, self).__init__()
         self.input_dim, self.hidden_dim, self.output_dim = input_dim, hidden_dim, output_dim
         self.augment_dim = augment_dim
         odefunc = ODEFunc(input_dim, hidden_dim, augment_dim, time_dependent, non_linearity)
-        self.odeblock = ODEBlock(odefunc, tol=tol, adjoint=adjoint, solver=solver)
+        self.odeblock = ODEBlock(odefunc, tol=tol, adjoint=adjoint, solver=solver, gradient=gradient)
         self.linear_layer = nn.Linear(odefunc.input_dim, output_dim)
 
     def forward(self, x, return_features=False):

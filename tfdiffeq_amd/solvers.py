@@ -392,6 +392,10 @@ def clear_engine_cache():
     while _ENGINE_CACHE:
         _, eng = _ENGINE_CACHE.popitem()
         eng.close()
+    import sys
+    disc = sys.modules.get(__package__ + '.discrete')        # the reverse-sweep engines and their activation scratch (discrete._ENGINES)
+    if disc is not None:
+        disc.clear_engines()
 
 
 class SyncTimeout(RuntimeError):
