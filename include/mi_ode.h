@@ -232,7 +232,7 @@ const char* mi_ode_last_error(void);                      /* thread-local text o
 int64_t mi_ode_reduce_workspace_bytes(void);              /* scratch the stateless reductions need */
 int64_t mi_ode_sizeof(int32_t which);                     /* 0: mi_ode_desc, 1: mi_ode_stats, 2: mi_ode_tableau, 3: mi_ode_rhs,
                                                              5: mi_ode_ctrl_params, 6: mi_ode_adjoint_desc, 7: mi_ode_opq_desc, 8: mi_ode_linadj_desc,
-                                                             9: mi_ode_discrete_desc
+                                                             9: mi_ode_discrete_desc, 10: mi_ode_discrete_row_desc
                                                              (lets a foreign-language binding verify its struct layout) */
 
 /* ---- (A) fused engine ---------------------------------------------------------------------- */
@@ -421,6 +421,30 @@ int64_t mi_ode_discrete_num_params(mi_ode_discrete_handle h);
  * done; returns status bits (>= 0) or an error (< 0).  stats->n_launches == 1. */
 int mi_ode_discrete_sweep(mi_ode_discrete_handle h, const mi_ode_rhs* rhs, const double* t_host, const void* ys_dev,
                           const void* grad_ys_dev, void* grad_y0_out_dev, void* grad_theta_out_dev, mi_ode_stats* stats, void* stream);
+
+/* ---- (A''''') the same reverse sweep for a row-local f with a generated vjp (tfdiffeq_amd/lower.py), ONE launch ------------------------ */
+/* rhs: MI_ODE_RHS_PLUGIN with `plugin` = what a discrete plugin's mi_ode_discrete_plugin_get(dtype) returned (csrc/mi_ode_discrete_plugin.h);
+ * scalars and w[0] as for the row-local plugin of the same callable.  A trajectory per lane; the parameter gradient is reduced in a fixed
+ * order (lanes, wavefronts, workgroups - the last workgroup to arrive folds): two calls give identical bits, no workgroup waits for another.
+ * fp32 or fp64.  The caller owns the small device buffers (nothing is allocated here). */
+typedef struct mi_ode_discrete_row_desc {
+  int32_t dtype;              /* MI_ODE_F32 / MI_ODE_F64 */
+  int32_t n_points;           /* grid points N (N - 1 steps), N >= 2 */
+  int64_t batch;
+  int32_t dim;                /* <= 32, the plugin's */
+  int32_t n_params;           /* P <= 1024: trainable elements, the plugin's */
+  int32_t grid;               /* workgroups, 1 .. min(1024, ceil(batch / 256)) */
+  int32_t reserved;
+  mi_ode_tableau tableau;     /* explicit, 0, 1 or 3 rows (1, 2 or 4 stages): beta = a_ij, c_sol = b */
+  const double* t_dev;        /* device: the N grid times, float64 (values already rounded to the state dtype) */
+  void* partials_dev;         /* device workspace: grid * P elements of the state dtype */
+  void* ticket_dev;           /* device: one zeroed 32-bit word (left zero again) */
+} mi_ode_discrete_row_desc;
+/* ys_dev: the forward solution [N, batch, dim]; grad_ys_dev: the gradient of the loss with respect to it; grad_y0_out_dev [batch, dim];
+ * grad_theta_out_dev [P] in the compact order of the generated vjp.  Enqueues one launch on `stream`; returns 0 or a negative MI_ODE_E_*
+ * (MI_ODE_E_INVALID for a null / inconsistent descriptor or another table in rhs->plugin, MI_ODE_E_NODEVICE without a device). */
+int mi_ode_discrete_row_sweep(const mi_ode_discrete_row_desc* desc, const mi_ode_rhs* rhs, const void* ys_dev, const void* grad_ys_dev,
+                              void* grad_y0_out_dev, void* grad_theta_out_dev, mi_ode_stats* stats, void* stream);
 
 /* ---- function-level parity surface of the step controller ----------------------------------- */
 /* The scalar tail of one step attempt exactly as the kernels run it (csrc/mi_ode_ctrl_dev.h, ONE device thread per case):

@@ -97,6 +97,16 @@ class DiscreteDesc(C.Structure):
                 ('n_points', C.c_int32), ('chunk_tiles', C.c_int32)]
 
 
+class DiscreteRowDesc(C.Structure):
+    """mi_ode_discrete_row_desc: the reverse sweep of a fixed-grid solve of a lowered row-local callable in one launch."""
+    _fields_ = [('dtype', C.c_int32), ('n_points', C.c_int32), ('batch', C.c_int64), ('dim', C.c_int32), ('n_params', C.c_int32),
+                ('grid', C.c_int32), ('reserved', C.c_int32), ('tableau', Tableau),
+                ('t_dev', C.c_void_p), ('partials_dev', C.c_void_p), ('ticket_dev', C.c_void_p)]
+
+
+DISCRETE_ROW_MAX_PARAMS, DISCRETE_ROW_THREADS, DISCRETE_ROW_MAX_GRID = 1024, 256, 1024
+
+
 class OpqDesc(C.Structure):
     """mi_ode_opq_desc: adaptive RK over an opaque (Python) right-hand side with the controller on the device."""
     _fields_ = [('dtype', C.c_int32), ('n_comp', C.c_int32), ('n', C.c_int64 * MAX_SEGMENTS), ('tableau', Tableau),
@@ -201,6 +211,8 @@ _PROTOS = {
     'mi_ode_discrete_num_params': (C.c_int64, [C.c_void_p]),
     'mi_ode_discrete_sweep': (C.c_int, [C.c_void_p, C.POINTER(Rhs), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_discrete_row_sweep': (C.c_int, [C.POINTER(DiscreteRowDesc), C.POINTER(Rhs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(Stats), C.c_void_p]),
     'mi_ode_opq_create': (C.c_int, [C.POINTER(OpqDesc), C.POINTER(C.c_void_p)]),
     'mi_ode_opq_destroy': (C.c_int, [C.c_void_p]),
     'mi_ode_opq_dt_dev': (C.c_void_p, [C.c_void_p]),
@@ -283,7 +295,7 @@ def load():
         fn.argtypes = args
     if lib.mi_ode_abi_version() != ABI_VERSION:
         raise NativeError('libmi_ode.so ABI version mismatch')
-    for which, st in ((0, Desc), (1, Stats), (2, Tableau), (3, Rhs), (5, CtrlParams), (6, AdjointDesc), (7, OpqDesc), (8, LinAdjDesc), (9, DiscreteDesc)):
+    for which, st in ((0, Desc), (1, Stats), (2, Tableau), (3, Rhs), (5, CtrlParams), (6, AdjointDesc), (7, OpqDesc), (8, LinAdjDesc), (9, DiscreteDesc), (10, DiscreteRowDesc)):
         if lib.mi_ode_sizeof(which) != C.sizeof(st):
             raise NativeError('struct layout mismatch for %s: C %d vs ctypes %d'
                               % (st.__name__, lib.mi_ode_sizeof(which), C.sizeof(st)))

@@ -57,6 +57,7 @@ extern "C" int64_t mi_ode_sizeof(int32_t which) {
     case 7: return (int64_t)sizeof(mi_ode_opq_desc);
     case 8: return (int64_t)sizeof(mi_ode_linadj_desc);
     case 9: return (int64_t)sizeof(mi_ode_discrete_desc);
+    case 10: return (int64_t)sizeof(mi_ode_discrete_row_desc);
     default: return -1;
   }
 }

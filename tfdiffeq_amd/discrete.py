@@ -13,7 +13,10 @@ lambda_{n+1} = dL/dy_{n+1}, for i = s .. 1:
 and lambda_n = lambda_{n+1} + sum_i Ybar_i + gbar_n (gbar_n: the output gradient at grid point n).  The forward solution on the default
 grid holds every y_n, so the checkpoints are free and each step is recomputed from its own.
 
-Two engines:
+Three engines:
+  * fused row-local sweep - opt-in (`lower='auto'` / True, module default LOWER): a plain Python callable the tracer lowers to a row-local
+    program (lower.py, state of up to 32 elements per trajectory) gets the vjp of its trace as generated device code, and the whole
+    backward, all steps, is ONE launch with a trajectory per lane (csrc/mi_ode_discrete_row.h), float32 and float64;
   * fused mlp sweep - models.ODEFunc / rhs.MLP (relu, softplus, tanh), float32, time independent, dim <= 64, hidden <= 128, all six
     parameters trainable: the whole backward, all steps, is ONE launch (csrc/mi_ode_discrete.h);
   * generic sweep   - any `func`, any dtype, tuple states: per step one taped re-evaluation in torch ops and one torch.autograd.grad call.
@@ -42,6 +45,9 @@ TABLEAUS['huen'] = TABLEAUS['heun']
 FUSED = True                  # False: every call takes the generic sweep
 CHUNK_TILES = 0               # 32-row tiles of a workgroup that share one weight-gradient pass of the fused kernel; 0: all of them,
                               # as far as 1 GiB of activation scratch goes
+LOWER = False                 # default of odeint_discrete(lower=...): False - today's routes; 'auto' - the fused row-local sweep where it applies;
+                              # True - raise ValueError where it does not
+ROW_GRID = 0                  # workgroups of the fused row-local sweep; 0: one per 256 trajectories, up to 1024
 _ENGINES = {}
 
 
@@ -203,6 +209,121 @@ def _fused_plan(func, params, method, tensor_input, like):
     return (eng, mlp), ''
 
 
+class _RowPlan(object):
+    """What the fused row-local sweep of ONE call needs: the discrete plugin's table, the trace's parameter layout and a copy of the
+    constants the forward call was bound with (the program's pool buffer is shared: the next odeint of the same program overwrites it)."""
+
+    def __init__(self, lib, table, tr, targets, n_params, pool, scalars):
+        self.lib, self.table, self.trace, self.targets, self.n_params, self.pool, self.scalars = lib, table, tr, targets, n_params, pool, scalars
+        self.dim = 1
+        for s_ in tr.tail:
+            self.dim *= int(s_)
+
+
+def _row_plan(func, params, method, y0, build=True):
+    """(_RowPlan, '') when the fused row-local sweep takes this call, else (None, why not).  Traces, classifies, generates the vjp and
+    builds the plugin - at the call, not in backward."""
+    from . import lower as L
+    if not isinstance(y0, torch.Tensor):
+        return None, 'a tuple state (the fused row-local sweep takes one state tensor)'
+    if y0.dtype not in (torch.float32, torch.float64):
+        return None, 'dtype %s (the fused row-local sweep is float32 / float64)' % str(y0.dtype).replace('torch.', '')
+    if method not in TABLEAUS:
+        return None, 'method %r' % (method,)
+    if getattr(func, 'kind', 0) or getattr(func, 'stage_rhs', None) is not None or not callable(func):
+        return None, 'a device right-hand side descriptor, not a Python callable'
+    try:
+        if isinstance(func, L.CompiledCallable):
+            tr = func._trace_for(y0, method)
+        else:
+            tr, _hit = L._cached_trace(func, y0, None) if L.TRACE_CACHE else (None, False)
+            if tr is None:
+                tr = L.trace(func, y0)
+        rows = 1
+        for s_ in tr.batch_shape:
+            rows *= int(s_)
+        kind, _info = L.classify(tr, rows=rows)
+    except L.TraceError as e:
+        return None, 'the callable cannot be lowered: %s' % e
+    except Exception as e:                               # the callable itself failed on the proxies
+        return None, 'tracing failed: %s: %s' % (type(e).__name__, e)
+    if kind != 'rowlocal':
+        return None, 'the callable lowers to the %r family, which has no generated vjp (row-local programs do)' % kind
+    plist, n_params = L.vjp_params(tr)
+    targets = []
+    for idx, off, n in plist:
+        e = tr.tensors[idx]
+        x = e['t']
+        if not x.is_leaf:
+            return None, 'a derived (non-leaf) trainable tensor of shape %s enters the callable (W.t(), a slice, a product): the kernel ' \
+                         'differentiates with respect to the tensors the trace reads' % (list(x.shape),)
+        if e['lead'] != 0:
+            return None, 'a trainable constant of shape %s with batch axes (every trajectory would need its own copy of the gradient)' % (list(x.shape),)
+        k = [j for j, p_ in enumerate(params) if p_ is x]
+        if not k:
+            return None, 'the trace reads a trainable tensor of shape %s that the parameter search did not find' % (list(x.shape),)
+        targets.append((k[0], off, n))
+    for req in tr.tensors:
+        if req['t'].requires_grad and not req['t'].dtype.is_floating_point:
+            return None, 'a trainable tensor of dtype %s' % req['t'].dtype
+    missing = [p_ for j, p_ in enumerate(params) if all(k != j for k, _o, _n in targets)]
+    if missing:
+        return None, 'a trainable tensor of shape %s does not enter the trace as it is (it is used through a derived tensor, or not at all)' \
+                     % (list(missing[0].shape),)
+    if n_params > N.DISCRETE_ROW_MAX_PARAMS:
+        return None, '%d trainable elements (the kernel keeps up to %d per wavefront in LDS)' % (n_params, N.DISCRETE_ROW_MAX_PARAMS)
+    try:
+        source = L.discrete_source(tr)
+    except L.TraceError as e:
+        return None, str(e)
+    if not y0.is_cuda:
+        return None, 'a host tensor'
+    if not build:
+        return source, ''
+    from . import rhs as R
+    try:
+        lib, table = R.discrete_plugin(source, y0.dtype)
+    except N.NativeError as e:
+        return None, 'the generated vjp did not compile (%s)' % str(e).split(';')[0]
+    prog = L.program_for(tr)
+    bound = prog.bind(tr, y0.device)
+    pool = None if bound.pool is None else bound.pool.clone()
+    return _RowPlan(lib, table, tr, targets, n_params, pool, list(bound.params)), ''
+
+
+def _row_sweep(plan, method, t, ys, grad_ys):
+    """(grad_y0 [batch, dim], grad_theta [P] in the trace's compact order, n_launches) - ys / grad_ys: [N, batch, dim], contiguous."""
+    from .solvers import _fill_tableau
+    n_pts, batch, dim = (int(v) for v in ys.shape)
+    dev, dtype = ys.device, ys.dtype
+    groups = (batch + N.DISCRETE_ROW_THREADS - 1) // N.DISCRETE_ROW_THREADS
+    grid = min(groups, N.DISCRETE_ROW_MAX_GRID)
+    if int(ROW_GRID) > 0:
+        grid = max(1, min(int(ROW_GRID), grid))
+    P = plan.n_params
+    d = N.DiscreteRowDesc()
+    d.dtype, d.n_points, d.batch, d.dim, d.n_params, d.grid = N.dtype_code(dtype), n_pts, batch, dim, P, grid
+    _fill_tableau(d.tableau, TABLEAUS[method], None)
+    t_dev = torch.as_tensor(t).detach().to(dtype).to(device=dev, dtype=torch.float64).contiguous()
+    words = grid * max(P, 1)
+    work = torch.zeros(words + 2, dtype=dtype, device=dev)   # [grid, P] partials, then the ticket word (zeroed)
+    d.t_dev, d.partials_dev, d.ticket_dev = t_dev.data_ptr(), work.data_ptr(), work.data_ptr() + words * work.element_size()
+    r = N.Rhs()
+    r.kind, r.sign, r.plugin = N.RHS_PLUGIN, 1.0, plan.table
+    for i, v in enumerate(plan.scalars[:8]):
+        r.scalars[i] = v
+    if plan.pool is not None:
+        r.w[0] = plan.pool.data_ptr()
+    g_y0 = torch.empty(batch, dim, dtype=dtype, device=dev)
+    g_th = torch.empty(max(P, 1), dtype=dtype, device=dev)
+    stats = N.Stats()
+    with torch.cuda.device(dev):
+        N.check(N.load().mi_ode_discrete_row_sweep(C.byref(d), C.byref(r), ys.data_ptr(), grad_ys.data_ptr(), g_y0.data_ptr(), g_th.data_ptr(),
+                                                          C.byref(stats), N.stream_ptr(dev)), 'mi_ode_discrete_row_sweep')
+    del t_dev, work
+    return g_y0, g_th, int(stats.n_launches)
+
+
 def _params_of(func, y0, t):
     """The tensors the gradient is taken with respect to, found the way odeint / odeint_adjoint find them: a module's grad-requiring
     parameters (then the bare tensors a wrapped callable carries), the grad-requiring leaves of a plain callable's evaluation."""
@@ -241,7 +362,21 @@ class _OdeintDiscrete(torch.autograd.Function):
         t = ctx.t.detach()
         grad_output = tuple(g if g is not None else torch.zeros_like(a) for g, a in zip(grad_output, ans))
         n_steps = int(like.shape[0]) - 1
+        row, row_why = getattr(ctx, 'row_plan', None) or (None, '')
+        if row is not None:
+            with torch.no_grad():
+                shape = like.shape
+                g_y0, theta, n_launches = _row_sweep(row, method, t, like.reshape(shape[0], -1, row.dim).contiguous(),
+                                                     grad_output[0].reshape(shape[0], -1, row.dim).contiguous())
+                gp = [None] * len(params)
+                for k, off, n in row.targets:
+                    gp[k] = theta[off:off + n].reshape(params[k].shape).to(params[k].dtype)
+            odeint_discrete.last_backward_stats = {'engine': 'fused row-local sweep', 'n_steps': n_steps, 'n_launches': n_launches, 'why': '',
+                                                   'method': method, 'n_params': row.n_params, 'forward': ctx.forward_stats}
+            return (None,) * 7 + tuple(gp) + (g_y0.reshape(shape[1:]),)
         plan, why = _fused_plan(func, params, method, ctx.tensor_input, like)
+        if row_why:
+            why = 'fused row-local sweep: %s; fused mlp sweep: %s' % (row_why, why)
         if plan is not None:
             from .adjoint import HandoffTimeout, canonical_to_module_order
             eng, mlp = plan
@@ -270,7 +405,20 @@ class _OdeintDiscrete(torch.autograd.Function):
         return (None,) * 7 + tuple(gp) + tuple(g_y0)
 
 
-def odeint_discrete(func, y0, t, method='rk4', options=None, _forward_func=None):
+class _OdeintDiscreteLowered(torch.autograd.Function):
+    """_OdeintDiscrete with the outcome of the row-local planning - (plan, '') or (None, why not) - in front of its arguments."""
+
+    @staticmethod
+    def forward(ctx, row_plan, *args):
+        ctx.row_plan = row_plan
+        return _OdeintDiscrete.forward(ctx, *args)
+
+    @staticmethod
+    def backward(ctx, *grad_output):
+        return (None,) + _OdeintDiscrete.backward(ctx, *grad_output)
+
+
+def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, _forward_func=None):
     """`odeint(func, y0, t, method=method, options=options)` - same values, same engine - whose result is differentiable with respect to
     y0 and func's trainable tensors, with the gradient of the DISCRETE map the solver computed (what back-propagating through the
     reference's solver gives), not the continuous adjoint's.
@@ -279,9 +427,15 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, _forward_func=None)
     adaptive and multistep methods, the step_size / grid_constructor / eps options, a `t` that requires grad - raises ValueError and
     names `odeint_adjoint`.  Adaptive solves over a recorded step sequence are out of scope.  Tensor and tuple states are accepted;
     parameters are found as odeint / odeint_adjoint find them (module parameters; the grad-requiring leaves of a plain callable).
-    `odeint_discrete.last_backward_stats`: {'engine': 'fused mlp sweep' | 'generic sweep', 'n_steps', 'n_launches', 'why'} of the last
-    backward ('why': the reason the fused kernel was not used)."""
+    lower: None - the module default `discrete.LOWER` (False); False - the routes above; 'auto' - a callable the tracer lowers to a row-local
+    program runs its whole backward in one launch (generated vjp, csrc/mi_ode_discrete_row.h), anything else falls to the routes above
+    with the reason in last_backward_stats['why']; True - ValueError with that reason, here at the call.
+    `odeint_discrete.last_backward_stats`: {'engine': 'fused row-local sweep' | 'fused mlp sweep' | 'generic sweep', 'n_steps',
+    'n_launches', 'why'} of the last backward ('why': the reason the fused kernels were not used)."""
     check_supported(method, options, t)
+    lower = LOWER if lower is None else lower
+    if lower not in (False, True, 'auto'):
+        raise ValueError("odeint_discrete: lower must be False, True or 'auto', not %r" % (lower,))
     tensor_input = isinstance(y0, torch.Tensor)
     ys = (y0,) if tensor_input else tuple(y0)
     for y_ in ys:
@@ -289,7 +443,14 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, _forward_func=None)
     t = torch.as_tensor(t)
     params = _params_of(func, y0, t) if torch.is_grad_enabled() else ()
     # (_forward_func: models.ODEBlock hands the forward solve the network's own fused descriptor, as its inference branch does)
-    out = _OdeintDiscrete.apply(func, func if _forward_func is None else _forward_func, method, options, t, tensor_input, len(params), *params, *ys)
+    fwd = func if _forward_func is None else _forward_func
+    if lower is not False:
+        row_plan = _row_plan(func, params, method, y0) if torch.is_grad_enabled() else (None, 'gradients are disabled')
+        if lower is True and row_plan[0] is None:
+            raise ValueError('odeint_discrete(lower=True): the fused row-local sweep does not take this call: ' + row_plan[1])
+        out = _OdeintDiscreteLowered.apply(row_plan, func, fwd, method, options, t, tensor_input, len(params), *params, *ys)
+        return out[0] if tensor_input else tuple(out)
+    out = _OdeintDiscrete.apply(func, fwd, method, options, t, tensor_input, len(params), *params, *ys)
     return out[0] if tensor_input else tuple(out)
 
 

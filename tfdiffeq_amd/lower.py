@@ -634,9 +634,9 @@ def _dispatch(name, args, kw):
         hi = kw.get('max', args[2] if len(args) > 2 else None)
         out = args[0]
         if lo is not None:
-            out = _ew(tr, 'max', (out, lo))
+            out = _ew(tr, 'max', (out, lo), attr='clamp')       # (attr: the gradient convention only - clamp passes it on its closed interval)
         if hi is not None:
-            out = _ew(tr, 'min', (out, hi))
+            out = _ew(tr, 'min', (out, hi), attr='clamp')
         return out
     if name in ('elu', 'leaky_relu'):
         a = kw.get('alpha', kw.get('negative_slope', args[1] if len(args) > 1 else (1.0 if name == 'elu' else 0.01)))
@@ -1172,7 +1172,8 @@ class _RowCG(object):
             return _Arr(parts[0].name, shape)
         return self._arr([x for p_ in parts for x in self.atoms(p_).reshape(-1)], shape)
 
-    def body(self):
+    def forward(self):
+        """The statements that compute every live node; returns node id -> value (atoms or _Arr)."""
         tr, val = self.tr, {}
         for n in tr.live():
             a = [val[x.id] for x in n.args]
@@ -1228,6 +1229,10 @@ class _RowCG(object):
             val[n.id] = v
             if len(self.lines) > MAX_ROW_STATEMENTS:
                 raise TraceError('more than %d statements per evaluation in one-trajectory-per-thread form' % MAX_ROW_STATEMENTS)
+        return val
+
+    def body(self):
+        tr, val = self.tr, self.forward()
         outv = np.broadcast_to(self.atoms(val[tr.out.id]), tr.tail).reshape(-1)
         for i, s in enumerate(outv):
             self.lines.append('k[%d] = %s;' % (i, s))
@@ -1311,6 +1316,378 @@ def host_source(tr):
 
 def _indent(body, n):
     return '\n'.join(' ' * n + ln for ln in body.splitlines())
+
+
+# ---------------------------------------------------------------------------------------------
+# reverse mode over a row-local trace: ybar = (df/dy)^T kbar and the contributions (df/dtheta)^T kbar of the grad-requiring tensors
+# ---------------------------------------------------------------------------------------------
+# Partial derivatives of the elementwise functions, times the incoming gradient: {g} gradient of the result, {o} the result, {x} / {a} {b}
+# the operands.  Conventions are torch.autograd's (relu' = x > 0, abs' = sign, a maximum / minimum tie in halves, clamp closed, where to
+# the selected branch, pow's special cases).  Functions with a zero gradient are listed in _VJP_ZERO.
+_LN2, _LN10 = '(T)0.6931471805599453', '(T)2.302585092994046'
+_SIG = '((T)1 / ((T)1 + exp(-{x})))'
+_VJP_UN = {'neg': '-{g}', 'abs': '{g} * (T)(({x} > (T)0) - ({x} < (T)0))', 'sigmoid': '{g} * ({o} * ((T)1 - {o}))', 'relu': '({x} > (T)0 ? {g} : (T)0)',
+           'softplus': '({x} > (T)20 ? {g} : {g} * ' + _SIG + ')', 'square': '{g} * ((T)2 * {x})', 'cube': '{g} * ((T)3 * ({x} * {x}))',
+           'reciprocal': '-{g} * ({o} * {o})', 'rsqrt': '(T)-0.5 * {g} * ({o} * {o} * {o})', 'rsquare': '(T)-2 * {g} * ({o} / {x})',
+           'silu': '{g} * (' + _SIG + ' * ((T)1 + {x} * ((T)1 - ' + _SIG + ')))', 'sin': '{g} * cos({x})', 'cos': '-{g} * sin({x})',
+           'tan': '{g} * ((T)1 + {o} * {o})', 'exp': '{g} * {o}', 'log': '{g} / {x}', 'sqrt': '{g} / ((T)2 * {o})', 'tanh': '{g} * ((T)1 - {o} * {o})',
+           'sinh': '{g} * cosh({x})', 'cosh': '{g} * sinh({x})', 'asin': '{g} / sqrt((T)1 - {x} * {x})', 'acos': '-{g} / sqrt((T)1 - {x} * {x})',
+           'atan': '{g} / ((T)1 + {x} * {x})', 'log1p': '{g} / ((T)1 + {x})', 'expm1': '{g} * ({o} + (T)1)', 'exp2': '{g} * ({o} * ' + _LN2 + ')',
+           'log2': '{g} / ({x} * ' + _LN2 + ')', 'log10': '{g} / ({x} * ' + _LN10 + ')', 'erf': '{g} * ((T)1.1283791670955126 * exp(-({x} * {x})))'}
+_VJP_BIN = {'add': ('{g}', '{g}'), 'sub': ('{g}', '-{g}'), 'mul': ('{g} * {b}', '{g} * {a}'), 'div': ('{g} / {b}', '-{g} * ({o} / {b})'),
+            'max': ('{g} * ({a} > {b} ? (T)1 : ({a} == {b} ? (T)0.5 : (T)0))', '{g} * ({b} > {a} ? (T)1 : ({a} == {b} ? (T)0.5 : (T)0))'),
+            'min': ('{g} * ({a} < {b} ? (T)1 : ({a} == {b} ? (T)0.5 : (T)0))', '{g} * ({b} < {a} ? (T)1 : ({a} == {b} ? (T)0.5 : (T)0))'),
+            'atan2': ('{g} * ({b} / ({a} * {a} + {b} * {b}))', '-{g} * ({a} / ({a} * {a} + {b} * {b}))'),
+            'pow': ('({b} == (T)0 ? (T)0 : {g} * ({b} * pow({a}, {b} - (T)1)))', '(({a} == (T)0 && {b} >= (T)0) ? (T)0 : {g} * ({o} * log({a})))')}
+_VJP_CLAMP = {'max': ('({a} >= {b} ? {g} : (T)0)', '({a} < {b} ? {g} : (T)0)'), 'min': ('({a} <= {b} ? {g} : (T)0)', '({a} > {b} ? {g} : (T)0)')}
+_VJP_ZERO = frozenset(('floor', 'ceil', 'sign', 'one', 'not', 'gt', 'lt', 'ge', 'le', 'eq', 'ne', 'and', 'or'))
+
+
+def vjp_params(tr):
+    """[(index into tr.tensors, offset in the compact parameter vector, elements)] of the grad-requiring tensors of a trace, and their
+    total: what the `acc.add(i, value)` calls of the generated vjp index."""
+    out, off = [], 0
+    for i, e in enumerate(tr.tensors):
+        if e['t'].requires_grad and e['t'].dtype.is_floating_point:
+            n = _prod(e['shape'])
+            out.append((i, off, n))
+            off += n
+    return out, off
+
+
+class _RowVjpCG(_RowCG):
+    """Straight-line reverse mode next to the forward statements of _RowCG.  The forward values are recomputed first (what the reverse pass
+    does not read, the compiler drops); then `tr.live()` is walked backwards.  The gradient of node n is the thread-private array gN,
+    indexed by constants wherever the forward code is written out; values wider than WIDE and the loop forms of _matvec get loops.  A
+    contribution to a trainable tensor goes to `acc.add(i, value)`: once per element from a local gN for tensors of up to WIDE elements,
+    straight from the product's loop for wider ones.  Nodes that depend neither on y nor on a trainable tensor get no code."""
+
+    def __init__(self, tr):
+        super(_RowVjpCG, self).__init__(tr)
+        self.par_off = {i: off for i, off, _n in vjp_params(tr)[0]}
+
+    def _g(self, m, i):
+        return 'g%d[%s]' % (m.id, i)
+
+    def _direct(self, m):
+        return m.op == 'ten' and m.size > WIDE
+
+    def add_to(self, m, i, expr):
+        """gradient of element i (an int or a C expression) of node m += expr"""
+        if m.id not in self.need:
+            return
+        if self._direct(m):
+            off = self.par_off[m.attr]
+            self.lines.append('acc.add(%s, %s);' % (off + i if isinstance(i, int) else '%d + %s' % (off, i), expr))
+        else:
+            self.lines.append('%s += %s;' % (self._g(m, i), expr))
+
+    def _ew_partials(self, n, xs, o, g):
+        """The gradient expressions of the operands of elementwise node n (None: no gradient)."""
+        fn, attr = n.attr
+        xs = ['(%s)' % x for x in xs]
+        if fn in _VJP_ZERO:
+            return [None] * len(xs)
+        if fn == 'where':
+            return [None, '(%s ? %s : (T)0)' % (xs[0], g), '(%s ? (T)0 : %s)' % (xs[0], g)]
+        if fn == 'powc':
+            return ['%s * (%s * pow(%s, %s))' % (g, _flit(attr), xs[0], _flit(attr - 1.0))]
+        if fn in _VJP_UN:
+            return [_VJP_UN[fn].format(g=g, o=o, x=xs[0])]
+        table = _VJP_CLAMP if attr == 'clamp' and fn in _VJP_CLAMP else _VJP_BIN
+        return [e.format(g=g, o=o, a=xs[0], b=xs[1]) for e in table[fn]]
+
+    def _ew_rev(self, n, a, v):
+        maps = [np.broadcast_to(np.arange(max(m.size, 1), dtype=np.int64).reshape(m.shape), n.shape).reshape(-1) for m in n.args]
+        if n.size > WIDE:
+            ops, tgt = [], []
+            for val, m, mp in zip(a, n.args, maps):
+                if m.size == 1:
+                    ops.append(self.atoms(val).reshape(-1)[0])
+                    tgt.append('0')
+                elif isinstance(val, _Arr) and val.shape == n.shape:
+                    ops.append('%s[i_]' % val.name)
+                    tgt.append('i_')
+                else:
+                    full = np.broadcast_to(self.atoms(val), n.shape).reshape(-1)
+                    ops.append('%s[i_]' % self.carray(list(full), m.is_bool))
+                    if m.id in self.need and not np.array_equal(mp, np.arange(n.size)):
+                        name = self._new('ix')
+                        self.lines.append('const int %s[%d] = {%s};' % (name, n.size, ', '.join(str(int(j)) for j in mp)))
+                        tgt.append('%s[i_]' % name)
+                    else:
+                        tgt.append('i_')
+            parts = self._ew_partials(n, ops, '%s[i_]' % v.name, self._g(n, 'i_'))
+            for m, e, tg in zip(n.args, parts, tgt):
+                if e is not None and m.id in self.need:
+                    self.lines.append('for (int i_ = 0; i_ < %d; ++i_) {' % n.size)
+                    self.add_to(m, tg, e)
+                    self.lines.append('}')
+            return
+        flat = [np.broadcast_to(self.atoms(val), n.shape).reshape(-1) for val in a]
+        outs = np.broadcast_to(self.atoms(v), n.shape).reshape(-1)
+        for i in range(n.size):
+            parts = self._ew_partials(n, [f_[i] for f_ in flat], outs[i], self._g(n, i))
+            for m, e, mp in zip(n.args, parts, maps):
+                if e is not None:
+                    self.add_to(m, int(mp[i]), e)
+
+    def _matvec_rev(self, n, g_off, x, xm, x_off, K, E, w_at, wm, w_ix, bm):
+        """Reverse of out[i] = sum_j x[j] * w(j, i) (+ bias[i]) for one row: x the row's forward value (atoms or _Arr) of node xm at flat
+        offset x_off, wm the constant node with flat index w_ix(j, i), bm the bias node or None; the gradient of the row is gN[g_off + i]."""
+        if K * E <= UNROLL_MACS:
+            x_atoms = list(self.atoms(x).reshape(-1))
+            for i in range(E):
+                g = self._g(n, g_off + i)
+                for j in range(K):
+                    self.add_to(xm, x_off + j, '%s * %s' % (g, w_at(j, i)))
+                    self.add_to(wm, w_ix(j, i), '%s * %s' % (g, x_atoms[j]))
+                if bm is not None:
+                    self.add_to(bm, i, g)
+            return
+        xa = x.name if isinstance(x, _Arr) else self.carray(list(x.reshape(-1)))
+        self.lines.append('for (int i_ = 0; i_ < %d; ++i_) {' % E)
+        self.lines.append('  const T gi_ = g%d[%d + i_];' % (n.id, g_off))
+        if bm is not None:
+            self.add_to(bm, 'i_', 'gi_')
+        self.lines.append('  for (int j_ = 0; j_ < %d; ++j_) {' % K)
+        self.add_to(xm, '%d + j_' % x_off, 'gi_ * %s' % w_at('j_', 'i_'))
+        self.add_to(wm, w_ix('j_', 'i_'), 'gi_ * %s[j_]' % xa)
+        self.lines.append('  }')
+        self.lines.append('}')
+
+    @staticmethod
+    def _lin_ix(stride_j, stride_i):
+        def ix(j, i):
+            if isinstance(j, int) and isinstance(i, int):
+                return j * stride_j + i * stride_i
+            return '%s * %d + %s * %d' % (j, stride_j, i, stride_i)
+        return ix
+
+    def _product_rev(self, n, a):
+        if n.op == 'linear':
+            x, w = n.args[0], n.args[1]
+            E, K = w.shape
+            wat = self._const_at(w)
+            bm = n.args[2] if len(n.args) > 2 else None
+            for r, row in enumerate(self._rows(a[0], x, K)):
+                self._matvec_rev(n, r * E, row, x, r * K, K, E, lambda j, i: wat(i, j), w, self._lin_ix(1, K), bm)
+            return
+        x, w = n.args
+        if w.op == 'ten' and w.rank == 2 and x.rank >= 1:
+            K, E = w.shape
+            wat = self._const_at(w)
+            for r, row in enumerate(self._rows(a[0], x, K)):
+                self._matvec_rev(n, r * E, row, x, r * K, K, E, lambda j, i: wat(j, i), w, self._lin_ix(E, 1), None)
+            return
+        if x.op == 'ten' and x.rank == 2 and w.rank in (1, 2) and (w.rank == 1 or w.shape[1] == 1):
+            E, K = x.shape
+            xat = self._const_at(x)
+            row = self._rows(a[1], w, K)[0] if w.rank == 1 else a[1] if isinstance(a[1], _Arr) else np.broadcast_to(self.atoms(a[1]), w.shape).reshape(-1)
+            self._matvec_rev(n, 0, row, w, 0, K, E, lambda j, i: xat(i, j), x, self._lin_ix(1, K), None)
+            return
+        A, B = np.broadcast_to(self.atoms(a[0]), x.shape), np.broadcast_to(self.atoms(a[1]), w.shape)
+        ia, ib = np.arange(x.size, dtype=np.int64).reshape(x.shape), np.arange(w.size, dtype=np.int64).reshape(w.shape)
+
+        def mats(m, left):
+            m2 = (m.reshape((1,) + m.shape) if left else m.reshape(m.shape + (1,))) if m.ndim == 1 else m
+            return m2
+        a2, b2, ia2, ib2 = mats(A, True), mats(B, False), mats(ia, True), mats(ib, False)
+        lead = np.broadcast_shapes(a2.shape[:-2], b2.shape[:-2])
+        bc = lambda m: np.broadcast_to(m, lead + m.shape[-2:]).reshape((-1,) + m.shape[-2:])       # noqa: E731
+        o = 0
+        for am, bm_, iam, ibm in zip(bc(a2), bc(b2), bc(ia2), bc(ib2)):
+            for i in range(am.shape[0]):
+                for j in range(bm_.shape[1]):
+                    g = self._g(n, o)
+                    for k_ in range(am.shape[1]):
+                        self.add_to(x, int(iam[i, k_]), '%s * %s' % (g, bm_[k_, j]))
+                        self.add_to(w, int(ibm[k_, j]), '%s * %s' % (g, am[i, k_]))
+                    o += 1
+
+    def vjp_body(self):
+        tr = self.tr
+        val = self.forward()
+        live = tr.live()
+        need = set()
+        for n in live:
+            if n.is_bool:
+                continue
+            if n.op == 'y' or (n.op == 'ten' and n.attr in self.par_off) or any(m.id in need for m in n.args):
+                need.add(n.id)
+        self.need = need
+        self.lines.append('// reverse')
+        for n in live:
+            if n.id in need and not self._direct(n):
+                self.lines.append('T g%d[%d] = {};' % (n.id, max(n.size, 1)))
+        if tr.out.id in need:
+            for i in range(_prod(tr.tail)):
+                self.lines.append('g%d[%d] += kbar[%d];' % (tr.out.id, i, i))
+        ynode = None
+        for n in reversed(live):
+            if n.id not in need:
+                continue
+            a = [val[x.id] for x in n.args]
+            if n.op == 'y':
+                ynode = n
+            elif n.op == 'ten':
+                if not self._direct(n):
+                    off = self.par_off[n.attr]
+                    for i in range(max(n.size, 1)):
+                        self.lines.append('acc.add(%d, g%d[%d]);' % (off + i, n.id, i))
+            elif n.op == 'ew':
+                self._ew_rev(n, a, val[n.id])
+            elif n.op == 'gather':
+                src, idx = n.attr
+                flat_idx = idx.reshape(-1)
+                if src is None and n.size > WIDE and n.args[0].size == n.size and np.array_equal(flat_idx, np.arange(n.size)) and not self._direct(n.args[0]):
+                    self.lines.append('for (int i_ = 0; i_ < %d; ++i_) g%d[i_] += g%d[i_];' % (n.size, n.args[0].id, n.id))
+                else:
+                    srcf = None if src is None else src.reshape(-1)
+                    for i_, j_ in enumerate(flat_idx):
+                        self.add_to(n.args[0 if srcf is None else int(srcf[i_])], int(j_), self._g(n, i_))
+            elif n.op in ('linear', 'matmul'):
+                self._product_rev(n, a)
+            elif n.op == 'sum':
+                axes, keep = n.attr
+                m = n.args[0]
+                src = np.arange(m.size, dtype=np.int64).reshape(m.shape)
+                moved = np.moveaxis(src, axes, tuple(range(-len(axes), 0)))
+                moved = moved.reshape(moved.shape[:moved.ndim - len(axes)] + (-1,))
+                for i, r in enumerate(moved.reshape(-1, moved.shape[-1])):
+                    for j in r:
+                        self.add_to(m, int(j), self._g(n, i))
+            else:
+                raise AssertionError(n.op)
+            if len(self.lines) > MAX_ROW_STATEMENTS:
+                raise TraceError('more than %d statements for the evaluation and its reverse pass in one-trajectory-per-thread form' % MAX_ROW_STATEMENTS)
+        for i in range(_prod(tr.tail)):
+            self.lines.append('ybar[%d] = %s;' % (i, 'g%d[%d]' % (ynode.id, i) if ynode is not None else '(T)0'))
+        return '\n'.join(self.lines)
+
+
+def rowlocal_vjp_body(tr):
+    return _RowVjpCG(tr).vjp_body()
+
+
+_HOST_VJP_TEMPLATE = """// host build of a generated right-hand side and its vjp (tests: the same statements, compiled by g++)
+#include <cmath>
+using namespace std;
+#define MI_ODE_ROW_HD
+template <typename T>
+struct RhsUser {{
+  static constexpr int D = {dim};
+  T p[8];
+  const T* cw;
+  RhsUser(const double* ps, const T* cw_) : cw(cw_) {{ for (int i = 0; i < 8; ++i) p[i] = (T)ps[i]; }}
+  void operator()(T t, const T* y, T* k) const {{
+    (void)t; (void)cw;
+{body}
+  }}
+  template <class ACC> void vjp(T t, const T* y, const T* kbar, T* ybar, ACC& acc) const {{
+    (void)t; (void)cw; (void)acc; (void)kbar;
+{vjp}
+  }}
+}};
+template <typename T> struct HostSink {{
+  T* g;
+  void add(int i, T v) {{ g[i] += v; }}
+}};
+template <typename T> static void vjp_(T t, const T* y, const T* kbar, T* ybar, T* theta_bar, const double* ps, const T* cw) {{
+  RhsUser<T> f(ps, cw);
+  HostSink<T> acc{{theta_bar}};
+  f.vjp(t, y, kbar, ybar, acc);
+}}
+extern "C" void vjp_f64(double t, const double* y, const double* kbar, double* ybar, double* theta_bar, const double* ps, const double* cw) {{
+  vjp_<double>(t, y, kbar, ybar, theta_bar, ps, cw);
+}}
+extern "C" void vjp_f32(float t, const float* y, const float* kbar, float* ybar, float* theta_bar, const double* ps, const float* cw) {{
+  vjp_<float>(t, y, kbar, ybar, theta_bar, ps, cw);
+}}
+"""
+
+_DISCRETE_TEMPLATE = """// generated by tfdiffeq_amd.lower from a traced Python callable: f and its vjp for the discrete reverse sweep - do not edit
+#define {dtype_macro} 1
+#include "mi_ode_discrete_plugin.h"
+namespace mi {{
+template <typename T>
+struct RhsUser {{
+  static constexpr int D = {dim};
+  static constexpr int P = {n_params};                     // grad-requiring elements: the range of acc.add's index
+  T p[8];
+  const T* cw;
+  __device__ explicit RhsUser(const RhsParams& r) : cw((const T*)r.w[0]) {{
+#pragma unroll
+    for (int i = 0; i < 8; ++i) p[i] = (T)r.s[i];
+  }}
+  __device__ __forceinline__ void operator()(T t, const T* y, T* k) const {{
+    (void)t; (void)cw;
+{body}
+  }}
+  template <class ACC>
+  __device__ __forceinline__ void vjp(T t, const T* y, const T* kbar, T* ybar, ACC& acc) const {{
+    (void)t; (void)cw; (void)acc; (void)kbar;
+{vjp}
+  }}
+}};
+}}  // namespace mi
+MI_ODE_DEFINE_DISCRETE_PLUGIN(mi::RhsUser)
+"""
+
+
+_HOST_SWEEP_DRIVER = """
+// the per-trajectory step of the reverse-sweep kernel (csrc/mi_ode_discrete_row.h) around the functor above, one trajectory after another
+#include "mi_ode_discrete_row.h"
+template <typename T, int S>
+static void sweep_(const mi::DiscreteRowTableau& tb, int N, int batch, const double* t, const T* ys, const T* gys, T* gy0, T* gtheta,
+                   const double* ps, const T* cw) {
+  constexpr int D = RhsUser<T>::D;
+  RhsUser<T> f(ps, cw);
+  HostSink<T> acc{gtheta};
+  for (int r = 0; r < batch; ++r) {
+    T lam[D], lam2[D];
+    for (int d = 0; d < D; ++d) lam[d] = gys[((long long)(N - 1) * batch + r) * D + d];
+    for (int n = N - 2; n >= 0; --n) {
+      const T tn = (T)t[n], h = (T)t[n + 1] - tn;
+      mi::discrete_row_step<T, S, D>(f, tb, ys + ((long long)n * batch + r) * D, tn, h, lam, lam2, acc);
+      for (int d = 0; d < D; ++d) lam[d] = lam2[d] + gys[((long long)n * batch + r) * D + d];
+    }
+    for (int d = 0; d < D; ++d) gy0[(long long)r * D + d] = lam[d];
+  }
+}
+extern "C" int sweep_f64(int S, const double* a16, const double* b4, const double* c4, int N, int batch, const double* t, const double* ys,
+                         const double* gys, double* gy0, double* gtheta, const double* ps, const double* cw) {
+  mi::DiscreteRowTableau tb;
+  for (int i = 0; i < 4; ++i) {
+    tb.b[i] = b4[i];
+    tb.c[i] = c4[i];
+    for (int j = 0; j < 4; ++j) tb.a[i][j] = a16[i * 4 + j];
+  }
+  if (S == 1) sweep_<double, 1>(tb, N, batch, t, ys, gys, gy0, gtheta, ps, cw);
+  else if (S == 2) sweep_<double, 2>(tb, N, batch, t, ys, gys, gy0, gtheta, ps, cw);
+  else if (S == 4) sweep_<double, 4>(tb, N, batch, t, ys, gys, gy0, gtheta, ps, cw);
+  else return -1;
+  return 0;
+}
+"""
+
+
+def host_sweep_source(tr):
+    """host_vjp_source plus `sweep_f64`: the whole reverse sweep on the host, through the step template the kernel uses (compile with
+    -I csrc)."""
+    return host_vjp_source(tr) + _HOST_SWEEP_DRIVER
+
+
+def host_vjp_source(tr):
+    """f and its vjp as host code (the CPU tests compile it with g++): `vjp_f64 / vjp_f32(t, y, kbar, ybar, theta_bar, ps, cw)` add the
+    parameter contributions into the plain array theta_bar (compact order of vjp_params)."""
+    return _HOST_VJP_TEMPLATE.format(dim=_prod(tr.tail), body=_indent(rowlocal_body(tr), 4), vjp=_indent(rowlocal_vjp_body(tr), 4))
+
+
+def discrete_source(tr):
+    """The discrete plugin of a row-local trace (csrc/mi_ode_discrete_plugin.h): the functor with operator() and vjp."""
+    return _DISCRETE_TEMPLATE.format(dtype_macro='MI_ODE_PLUGIN_F32' if tr.dtype == torch.float32 else 'MI_ODE_PLUGIN_F64', dim=_prod(tr.tail),
+                                     n_params=vjp_params(tr)[1], body=_indent(rowlocal_body(tr), 4), vjp=_indent(rowlocal_vjp_body(tr), 4))
 
 
 # ---------------------------------------------------------------------------------------------

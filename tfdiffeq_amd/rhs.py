@@ -481,6 +481,24 @@ class CustomRowLocal(DeviceRHS):
         return hit
 
 
+_DISCRETE_PLUGINS = {}
+
+
+def discrete_plugin(source, dtype):
+    """(library, address of the mi_ode_discrete_row_plugin table) of a discrete plugin translation unit (lower.discrete_source:
+    csrc/mi_ode_discrete_plugin.h, f and its generated vjp behind the reverse-sweep kernel); compiled once, cached by source and header hash."""
+    hit = _DISCRETE_PLUGINS.get((source, dtype))
+    if hit is None:
+        from . import _plugin_build
+        lib = _plugin_build.build_and_load(source)
+        table = lib.mi_ode_discrete_plugin_get(N.dtype_code(dtype))
+        if not table:
+            raise N.NativeError('discrete plugin exports no table for %s' % dtype)
+        hit = (lib, table)
+        _DISCRETE_PLUGINS[(source, dtype)] = hit
+    return hit
+
+
 def hyper_source_of(rowlocal_source):
     """A row-local plugin translation unit (mi_ode_plugin.h) turned into the hyper plugin of the same functor."""
     src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_hyper_plugin.h"')
