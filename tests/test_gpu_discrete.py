@@ -56,12 +56,15 @@ def kink_free_rows(func, y0, t, method, batch):
     return y0[keep[:batch]].contiguous()
 
 
-def build(geom, batch, method, n, act, seed, time_dependent=False):
-    """(float32 CPU network, y0, t, weights of the loss at every grid point) of a case."""
+def build(geom, batch, method, n, act, seed, time_dependent=False, t=None):
+    """(float32 CPU network, y0, t, weights of the loss at every grid point) of a case.  t: the grid (its n points), default
+    linspace(0, 1, n)."""
     torch.manual_seed(1000 + seed)
     func = models.ODEFunc(geom[0], geom[1], time_dependent=time_dependent, non_linearity=act)
     g = torch.Generator().manual_seed(2000 + seed)
-    t = torch.linspace(0., 1., n)
+    if t is None:
+        t = torch.linspace(0., 1., n)
+    assert t.shape[0] == n
     if act == 'relu':
         y0 = kink_free_rows(func, torch.randn(2 * batch, geom[0], generator=g), t, method, batch)
     else:
