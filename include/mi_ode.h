@@ -232,7 +232,7 @@ const char* mi_ode_last_error(void);                      /* thread-local text o
 int64_t mi_ode_reduce_workspace_bytes(void);              /* scratch the stateless reductions need */
 int64_t mi_ode_sizeof(int32_t which);                     /* 0: mi_ode_desc, 1: mi_ode_stats, 2: mi_ode_tableau, 3: mi_ode_rhs,
                                                              5: mi_ode_ctrl_params, 6: mi_ode_adjoint_desc, 7: mi_ode_opq_desc, 8: mi_ode_linadj_desc,
-                                                             9: mi_ode_discrete_desc, 10: mi_ode_discrete_row_desc
+                                                             9: mi_ode_discrete_desc, 10: mi_ode_discrete_row_desc, 11: mi_ode_discrete_linear_desc
                                                              (lets a foreign-language binding verify its struct layout) */
 
 /* ---- (A) fused engine ---------------------------------------------------------------------- */
@@ -445,6 +445,34 @@ typedef struct mi_ode_discrete_row_desc {
  * (MI_ODE_E_INVALID for a null / inconsistent descriptor or another table in rhs->plugin, MI_ODE_E_NODEVICE without a device). */
 int mi_ode_discrete_row_sweep(const mi_ode_discrete_row_desc* desc, const mi_ode_rhs* rhs, const void* ys_dev, const void* grad_ys_dev,
                               void* grad_y0_out_dev, void* grad_theta_out_dev, mi_ode_stats* stats, void* stream);
+
+/* ---- (A'''''') the same reverse sweep for the linear system f(y) = y W (+ b) on the matrix cores, ONE launch ------------------------ */
+/* The transpose of the fixed-grid map of MI_ODE_RHS_LINEAR (csrc/mi_ode_discrete_linear.h): Ybar_i = kbar_i W^T, Wbar += Y_i^T kbar_i,
+ * bbar += sum_rows kbar_i.  fp32 or fp64, dim <= 128 (smaller dims run zero padded on the 16 / 32 / 64 / 128 wide instantiations), at most
+ * 4 stages and 1024 steps.  A persistent grid of at most one workgroup per CU; the parameter gradient is reduced in a fixed order. */
+typedef struct mi_ode_discrete_linear_desc {
+  int32_t dtype;              /* MI_ODE_F32 / MI_ODE_F64 */
+  int32_t dim;                /* 1 .. 128 */
+  int64_t batch;
+  int32_t has_bias;           /* 0 / 1: must agree with rhs->b[0] of every sweep */
+  int32_t n_points;           /* grid points N (N - 1 steps), 2 <= N <= 1025 */
+  mi_ode_tableau tableau;     /* explicit, at most 3 rows (4 stages): beta = a_ij, c_sol = b */
+} mi_ode_discrete_linear_desc;
+typedef struct mi_ode_discrete_linear* mi_ode_discrete_linear_handle;
+/* MI_ODE_E_INVALID for dim < 1 or > 128, n_points < 2 or > 1025, more than 4 stages, a dtype other than fp32 / fp64. */
+int mi_ode_discrete_linear_create(const mi_ode_discrete_linear_desc* desc, mi_ode_discrete_linear_handle* out);
+int mi_ode_discrete_linear_destroy(mi_ode_discrete_linear_handle h);
+/* t_host: the N grid times (host).  ys_dev / grad_ys_dev [N, batch, dim]; grad_y0_out_dev [batch, dim]; grad_W_out_dev [dim, dim] in the
+ * [in, out] layout of W; grad_b_out_dev [dim] or NULL.  All device memory in the state dtype.  rhs: the MI_ODE_RHS_LINEAR descriptor
+ * (w[0] = W, b[0] = bias or NULL; sign is ignored); the weights are read at every call.  Deterministic: two calls give identical bits.
+ * Blocks until done; returns status bits (>= 0; MI_ODE_ST_SYNC_TIMEOUT when a grid hand-off timed out: nothing was committed) or an error
+ * (< 0).  stats->n_launches == 1. */
+int mi_ode_discrete_linear_sweep(mi_ode_discrete_linear_handle h, const mi_ode_rhs* rhs, const double* t_host, const void* ys_dev,
+                                 const void* grad_ys_dev, void* grad_y0_out_dev, void* grad_W_out_dev, void* grad_b_out_dev,
+                                 mi_ode_stats* stats, void* stream);
+/* Workgroup 0's clock of the last sweep, microseconds: out3 = {tile sweep (all steps, weight-gradient products included), partial-block
+ * store, final hand-off + fold}.  Returns the grid size, or MI_ODE_E_INVALID. */
+int mi_ode_discrete_linear_profile(mi_ode_discrete_linear_handle h, double* out3);
 
 /* ---- function-level parity surface of the step controller ----------------------------------- */
 /* The scalar tail of one step attempt exactly as the kernels run it (csrc/mi_ode_ctrl_dev.h, ONE device thread per case):

@@ -107,6 +107,15 @@ class DiscreteRowDesc(C.Structure):
 DISCRETE_ROW_MAX_PARAMS, DISCRETE_ROW_THREADS, DISCRETE_ROW_MAX_GRID = 1024, 256, 1024
 
 
+class DiscreteLinearDesc(C.Structure):
+    """mi_ode_discrete_linear_desc: the reverse sweep of a fixed-grid solve of f(y) = y W (+ b) in one launch, on the matrix cores."""
+    _fields_ = [('dtype', C.c_int32), ('dim', C.c_int32), ('batch', C.c_int64), ('has_bias', C.c_int32), ('n_points', C.c_int32),
+                ('tableau', Tableau)]
+
+
+DISCRETE_LINEAR_MAX_DIM, DISCRETE_MAX_STEPS = 128, 1024
+
+
 class OpqDesc(C.Structure):
     """mi_ode_opq_desc: adaptive RK over an opaque (Python) right-hand side with the controller on the device."""
     _fields_ = [('dtype', C.c_int32), ('n_comp', C.c_int32), ('n', C.c_int64 * MAX_SEGMENTS), ('tableau', Tableau),
@@ -213,6 +222,11 @@ _PROTOS = {
                                         C.POINTER(Stats), C.c_void_p]),
     'mi_ode_discrete_row_sweep': (C.c_int, [C.POINTER(DiscreteRowDesc), C.POINTER(Rhs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_discrete_linear_create': (C.c_int, [C.POINTER(DiscreteLinearDesc), C.POINTER(C.c_void_p)]),
+    'mi_ode_discrete_linear_destroy': (C.c_int, [C.c_void_p]),
+    'mi_ode_discrete_linear_sweep': (C.c_int, [C.c_void_p, C.POINTER(Rhs), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_discrete_linear_profile': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'mi_ode_opq_create': (C.c_int, [C.POINTER(OpqDesc), C.POINTER(C.c_void_p)]),
     'mi_ode_opq_destroy': (C.c_int, [C.c_void_p]),
     'mi_ode_opq_dt_dev': (C.c_void_p, [C.c_void_p]),
@@ -295,7 +309,8 @@ def load():
         fn.argtypes = args
     if lib.mi_ode_abi_version() != ABI_VERSION:
         raise NativeError('libmi_ode.so ABI version mismatch')
-    for which, st in ((0, Desc), (1, Stats), (2, Tableau), (3, Rhs), (5, CtrlParams), (6, AdjointDesc), (7, OpqDesc), (8, LinAdjDesc), (9, DiscreteDesc), (10, DiscreteRowDesc)):
+    for which, st in ((0, Desc), (1, Stats), (2, Tableau), (3, Rhs), (5, CtrlParams), (6, AdjointDesc), (7, OpqDesc), (8, LinAdjDesc), (9, DiscreteDesc), (10, DiscreteRowDesc),
+                      (11, DiscreteLinearDesc)):
         if lib.mi_ode_sizeof(which) != C.sizeof(st):
             raise NativeError('struct layout mismatch for %s: C %d vs ctypes %d'
                               % (st.__name__, lib.mi_ode_sizeof(which), C.sizeof(st)))

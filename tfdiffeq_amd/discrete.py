@@ -13,7 +13,10 @@ lambda_{n+1} = dL/dy_{n+1}, for i = s .. 1:
 and lambda_n = lambda_{n+1} + sum_i Ybar_i + gbar_n (gbar_n: the output gradient at grid point n).  The forward solution on the default
 grid holds every y_n, so the checkpoints are free and each step is recomputed from its own.
 
-Three engines:
+Four engines:
+  * fused linear sweep - opt-in (`linear='auto'` / True, module default LINEAR): f(t, y) = y W (+ b) - models.LinearODEFunc, or a callable the
+    tracer puts in the 'linear' family (`y @ W`, `y @ W + b`, torch.nn.Linear(d, d)) - float32 and float64, dim <= 128: the whole backward,
+    all steps, is ONE launch on the matrix cores (csrc/mi_ode_discrete_linear.h);
   * fused row-local sweep - opt-in (`lower='auto'` / True, module default LOWER): a plain Python callable the tracer lowers to a row-local
     program (lower.py, state of up to 32 elements per trajectory) gets the vjp of its trace as generated device code, and the whole
     backward, all steps, is ONE launch with a trajectory per lane (csrc/mi_ode_discrete_row.h), float32 and float64;
@@ -47,8 +50,11 @@ CHUNK_TILES = 0               # 32-row tiles of a workgroup that share one weigh
                               # as far as 1 GiB of activation scratch goes
 LOWER = False                 # default of odeint_discrete(lower=...): False - today's routes; 'auto' - the fused row-local sweep where it applies;
                               # True - raise ValueError where it does not
+LINEAR = False                # default of odeint_discrete(linear=...): False - today's routes; 'auto' - the fused linear sweep where it applies; True -
+                              # raise ValueError where it does not
 ROW_GRID = 0                  # workgroups of the fused row-local sweep; 0: one per 256 trajectories, up to 1024
 _ENGINES = {}
+_LINEAR_ENGINES = {}
 
 
 def check_supported(method, options=None, t=None):
@@ -164,8 +170,11 @@ def _cached_engine(*key):
 
 
 def clear_engines():
+    """Empties both engine caches.  The MLP engines are closed here.  A linear engine is only dropped: a call that has run forward and not
+    yet backward still holds it, so its device memory is released when the last such graph is gone, which need not be now."""
     while _ENGINES:
         _ENGINES.pop(next(iter(_ENGINES))).close()
+    _LINEAR_ENGINES.clear()                              # (dropped, not closed: see _cached_linear_engine)
 
 
 def _fused_plan(func, params, method, tensor_input, like):
@@ -207,6 +216,181 @@ def _fused_plan(func, params, method, tensor_input, like):
     except N.NativeError as e:                           # e.g. no memory for the activation scratch
         return None, 'the fused engine could not be created (%s)' % e
     return (eng, mlp), ''
+
+
+class _FusedLinearEngine(object):
+    """Owns one mi_ode_discrete_linear handle: the reverse sweep of `n_points - 1` steps of `method` for a [batch, dim] state and
+    f(y) = y W (+ b), one launch."""
+
+    def __init__(self, batch, dim, has_bias, method, n_points, device, dtype):
+        from .solvers import _fill_tableau
+        self.lib = N.load()
+        self.device = torch.device(device)
+        self.dtype = dtype
+        d = N.DiscreteLinearDesc()
+        d.dtype, d.dim, d.batch, d.has_bias, d.n_points = N.dtype_code(dtype), int(dim), int(batch), int(bool(has_bias)), int(n_points)
+        _fill_tableau(d.tableau, TABLEAUS[method], None)
+        self.desc = d
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            N.check(self.lib.mi_ode_discrete_linear_create(C.byref(d), C.byref(h)), 'mi_ode_discrete_linear_create')
+        self.h = h
+        self.batch, self.dim, self.n_points, self.has_bias = int(batch), int(dim), int(n_points), bool(has_bias)
+        self.stats = N.Stats()
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.mi_ode_discrete_linear_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def profile(self):
+        """{'grid', 'sweep_us', 'store_us', 'fold_us'} of the last sweep: workgroup 0's clock over the tile sweep (all steps, the weight-gradient
+        products included), the store of its partial block, the final hand-off and fold."""
+        out = (C.c_double * 3)()
+        g = self.lib.mi_ode_discrete_linear_profile(self.h, out)
+        return {'grid': int(g), 'sweep_us': out[0], 'store_us': out[1], 'fold_us': out[2]}
+
+    def sweep(self, W, b, t, ys, grad_ys):
+        """(grad_y0 [batch, dim], grad_W [dim, dim] in W's [in, out] layout, grad_b [dim] or None) from the forward solution and its
+        gradient, both [N, batch, dim].  W, b: device tensors in the state dtype, read now (nothing is cached between calls)."""
+        r = N.Rhs()
+        r.kind, r.sign, r.hidden = N.RHS_LINEAR, 1.0, 0
+        W = W.contiguous()
+        r.w[0] = W.data_ptr()
+        if b is not None:
+            b = b.contiguous()
+            r.b[0] = b.data_ptr()
+        ys, grad_ys = ys.contiguous(), grad_ys.contiguous()
+        g_y0 = torch.empty(self.batch, self.dim, dtype=self.dtype, device=self.device)
+        g_w = torch.empty(self.dim, self.dim, dtype=self.dtype, device=self.device)
+        g_b = torch.empty(self.dim, dtype=self.dtype, device=self.device) if b is not None else None
+        tt = (C.c_double * self.n_points)(*[float(v) for v in t])
+        with torch.cuda.device(self.device):
+            rc = N.check(self.lib.mi_ode_discrete_linear_sweep(self.h, C.byref(r), tt, ys.data_ptr(), grad_ys.data_ptr(), g_y0.data_ptr(), g_w.data_ptr(),
+                                                               None if g_b is None else g_b.data_ptr(), C.byref(self.stats),
+                                                               N.stream_ptr(self.device)), 'mi_ode_discrete_linear_sweep')
+        if rc != 0:
+            from .adjoint import HandoffTimeout
+            if rc & N.ST_SYNC_TIMEOUT:
+                raise HandoffTimeout(N.status_message(rc))
+            raise AssertionError(N.status_message(rc))
+        return g_y0, g_w, g_b
+
+
+def _cached_linear_engine(*key):
+    """The engine of `key`, four cached at most.  The plan of a call holds its engine from the call to its backward, so eviction (and
+    clear_engines) only drops the cache's reference: the handle is destroyed when the last pending plan lets go of it (__del__)."""
+    eng = _LINEAR_ENGINES.get(key)
+    if eng is None:
+        eng = _FusedLinearEngine(*key)                   # (evict only after a successful create: a refusal must not cost live engines)
+        while len(_LINEAR_ENGINES) >= 4:
+            _LINEAR_ENGINES.pop(next(iter(_LINEAR_ENGINES)))
+        _LINEAR_ENGINES[key] = eng
+    return eng
+
+
+def _on_device(x):
+    return x.is_cuda
+
+
+class _LinearPlan(object):
+    """What the fused linear sweep of ONE call needs: the parameters themselves (read at the backward, so an in-place optimizer step is
+    seen), how the matrix is laid out ('W': [in, out] as the kernel reads it; 'Wt': [out, in], torch.nn.Linear's), where their gradients
+    go among the call's parameters, and the engine."""
+
+    def __init__(self, W, b, how, slots, engine):
+        self.W, self.b, self.how, self.slots, self.engine = W, b, how, slots, engine
+
+    def sweep(self, t, ys, grad_ys, n_params):
+        dim = int(ys.shape[-1])
+        W = self.W.detach()
+        g_y0, g_w, g_b = self.engine.sweep(W if self.how == 'W' else W.t().contiguous(), None if self.b is None else self.b.detach().reshape(-1),
+                                           t, ys.reshape(ys.shape[0], -1, dim), grad_ys.reshape(ys.shape[0], -1, dim))
+        gp = [None] * n_params
+        gp[self.slots[0]] = (g_w if self.how == 'W' else g_w.t().contiguous()).reshape(self.W.shape)
+        if self.b is not None:
+            gp[self.slots[1]] = g_b.reshape(self.b.shape)
+        return g_y0, gp
+
+
+def _linear_plan(func, params, method, y0, like=None, n_points=None):
+    """(_LinearPlan, '') when the fused linear sweep takes this call, else (None, why not).  like: the solution (or any tensor of its
+    shape [N, ...]); without one, n_points is the number of grid points.  Creates (or finds) the engine - at the call, not in backward."""
+    from . import lower as L
+    from . import models as M
+    if not isinstance(y0, torch.Tensor):
+        return None, 'a tuple state (the fused linear sweep takes one state tensor)'
+    if y0.dtype not in (torch.float32, torch.float64):
+        return None, 'dtype %s (the fused linear sweep is float32 / float64)' % str(y0.dtype).replace('torch.', '')
+    if method not in TABLEAUS:
+        return None, 'method %r' % (method,)
+    if y0.dim() < 1:
+        return None, 'a 0-d state'
+    dim = int(y0.shape[-1])
+    if isinstance(func, M.LinearODEFunc):
+        if dim != func.dim:
+            return None, 'the state\'s last axis is %d, the module\'s dim %d' % (dim, func.dim)
+        W, b, how = func.weight, func.bias, 'W'
+    else:
+        if getattr(func, 'kind', 0) or getattr(func, 'stage_rhs', None) is not None or not callable(func):
+            return None, 'a device right-hand side descriptor, not a models.LinearODEFunc or a Python callable'
+        nfe = getattr(func, 'nfe', None)                 # (tracing runs a module's forward on proxies: not an evaluation the caller counts)
+        try:
+            if isinstance(func, L.CompiledCallable):
+                tr = func._trace_for(y0, method)
+            else:
+                tr, _hit = L._cached_trace(func, y0, None) if L.TRACE_CACHE else (None, False)
+                if tr is None:
+                    tr = L.trace(func, y0)
+            rows = 1
+            for s_ in tr.batch_shape:
+                rows *= int(s_)
+            kind, info = L.classify(tr, rows=rows)
+        except L.TraceError as e:
+            return None, 'the callable cannot be lowered: %s' % e
+        except Exception as e:                           # the callable itself failed on the proxies
+            return None, 'tracing failed: %s: %s' % (type(e).__name__, e)
+        finally:
+            if isinstance(nfe, int) and getattr(func, 'nfe', nfe) != nfe:
+                func.nfe = nfe
+        if kind != 'linear':
+            return None, 'the callable lowers to the %r family, not to y @ W (+ b)' % kind
+        how, widx = info['W']
+        ents = [tr.tensors[widx]] + ([] if info.get('b') is None else [tr.tensors[info['b']]])
+        for e in ents:
+            x = e['t']
+            if not x.is_leaf:
+                return None, 'a derived (non-leaf) tensor of shape %s enters the product (W.t(), tanh(W), a slice): the kernel differentiates ' \
+                             'with respect to the matrix and the bias the trace reads' % (list(x.shape),)
+            if e['lead'] != 0:
+                return None, 'a constant of shape %s with batch axes (every trajectory would need its own copy of the gradient)' % (list(x.shape),)
+        W = ents[0]['t']
+        b = ents[1]['t'] if len(ents) > 1 else None
+    if dim > N.DISCRETE_LINEAR_MAX_DIM:
+        return None, 'dim %d > %d (dims 129 .. 256 are forward-only on the streamed kernels)' % (dim, N.DISCRETE_LINEAR_MAX_DIM)
+    n_points = int(like.shape[0]) if like is not None else int(n_points)
+    if n_points - 1 > N.DISCRETE_MAX_STEPS:
+        return None, 'more than %d steps (%d)' % (N.DISCRETE_MAX_STEPS, n_points - 1)
+    want = [W] + ([] if b is None else [b])
+    slots = [next((j for j, p_ in enumerate(params) if p_ is w_), None) for w_ in want]
+    if len(params) != len(want) or any(j is None for j in slots):
+        return None, 'frozen or extra parameters (the kernel produces the gradients of exactly the matrix%s)' % ('' if b is None else ' and the bias')
+    if any(p_.dtype != y0.dtype or p_.device != y0.device for p_ in want):
+        return None, 'parameters in another dtype or on another device than the state'
+    if not _on_device(y0):
+        return None, 'a host tensor'
+    batch = y0.numel() // dim
+    try:
+        eng = _cached_linear_engine(batch, dim, b is not None, 'heun' if method == 'huen' else method, n_points, str(y0.device), y0.dtype)
+    except N.NativeError as e:
+        return None, 'the fused engine could not be created (%s)' % e
+    return _LinearPlan(W, b, how, slots, eng), ''
 
 
 class _RowPlan(object):
@@ -362,6 +546,17 @@ class _OdeintDiscrete(torch.autograd.Function):
         t = ctx.t.detach()
         grad_output = tuple(g if g is not None else torch.zeros_like(a) for g, a in zip(grad_output, ans))
         n_steps = int(like.shape[0]) - 1
+        lin, lin_why = getattr(ctx, 'linear_plan', None) or (None, '')
+        if lin is not None:
+            from .adjoint import HandoffTimeout
+            try:
+                with torch.no_grad():
+                    g_y0, gp = lin.sweep(t.to(like.dtype).double().cpu().numpy(), like, grad_output[0], len(params))
+                odeint_discrete.last_backward_stats = {'engine': 'fused linear sweep', 'n_steps': n_steps, 'n_launches': int(lin.engine.stats.n_launches),
+                                                       'why': '', 'method': method, 'forward': ctx.forward_stats}
+                return (None,) * 7 + tuple(gp) + (g_y0.reshape(like.shape[1:]),)
+            except HandoffTimeout as e:                  # the GPU is shared with another persistent kernel: nothing was committed
+                lin_why = 'the fused kernel\'s grid hand-off timed out (%s)' % e
         row, row_why = getattr(ctx, 'row_plan', None) or (None, '')
         if row is not None:
             with torch.no_grad():
@@ -377,6 +572,8 @@ class _OdeintDiscrete(torch.autograd.Function):
         plan, why = _fused_plan(func, params, method, ctx.tensor_input, like)
         if row_why:
             why = 'fused row-local sweep: %s; fused mlp sweep: %s' % (row_why, why)
+        if lin_why:
+            why = 'fused linear sweep: %s; %s' % (lin_why, why if row_why else 'fused mlp sweep: ' + why)
         if plan is not None:
             from .adjoint import HandoffTimeout, canonical_to_module_order
             eng, mlp = plan
@@ -418,7 +615,20 @@ class _OdeintDiscreteLowered(torch.autograd.Function):
         return (None,) + _OdeintDiscrete.backward(ctx, *grad_output)
 
 
-def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, _forward_func=None):
+class _OdeintDiscreteLinear(torch.autograd.Function):
+    """_OdeintDiscrete with the outcomes of the linear and the row-local planning (the latter None when `lower` is off) in front of its arguments."""
+
+    @staticmethod
+    def forward(ctx, linear_plan, row_plan, *args):
+        ctx.linear_plan, ctx.row_plan = linear_plan, row_plan
+        return _OdeintDiscrete.forward(ctx, *args)
+
+    @staticmethod
+    def backward(ctx, *grad_output):
+        return (None, None) + _OdeintDiscrete.backward(ctx, *grad_output)
+
+
+def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=None, _forward_func=None):
     """`odeint(func, y0, t, method=method, options=options)` - same values, same engine - whose result is differentiable with respect to
     y0 and func's trainable tensors, with the gradient of the DISCRETE map the solver computed (what back-propagating through the
     reference's solver gives), not the continuous adjoint's.
@@ -430,12 +640,19 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, _forwar
     lower: None - the module default `discrete.LOWER` (False); False - the routes above; 'auto' - a callable the tracer lowers to a row-local
     program runs its whole backward in one launch (generated vjp, csrc/mi_ode_discrete_row.h), anything else falls to the routes above
     with the reason in last_backward_stats['why']; True - ValueError with that reason, here at the call.
-    `odeint_discrete.last_backward_stats`: {'engine': 'fused row-local sweep' | 'fused mlp sweep' | 'generic sweep', 'n_steps',
+    linear: None - the module default `discrete.LINEAR` (False); False - the routes above; 'auto' - f(t, y) = y W (+ b) (models.LinearODEFunc, or a
+    callable the tracer puts in the 'linear' family: `y @ W`, `y @ W + b`, torch.nn.Linear(d, d)), float32 / float64, dim <= 128, runs its
+    whole backward in one launch on the matrix cores (csrc/mi_ode_discrete_linear.h), anything else falls to the routes above with the
+    reason in last_backward_stats['why']; True - ValueError with that reason, here at the call.
+    `odeint_discrete.last_backward_stats`: {'engine': 'fused linear sweep' | 'fused row-local sweep' | 'fused mlp sweep' | 'generic sweep', 'n_steps',
     'n_launches', 'why'} of the last backward ('why': the reason the fused kernels were not used)."""
     check_supported(method, options, t)
     lower = LOWER if lower is None else lower
     if lower not in (False, True, 'auto'):
         raise ValueError("odeint_discrete: lower must be False, True or 'auto', not %r" % (lower,))
+    linear = LINEAR if linear is None else linear
+    if linear not in (False, True, 'auto'):
+        raise ValueError("odeint_discrete: linear must be False, True or 'auto', not %r" % (linear,))
     tensor_input = isinstance(y0, torch.Tensor)
     ys = (y0,) if tensor_input else tuple(y0)
     for y_ in ys:
@@ -444,6 +661,17 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, _forwar
     params = _params_of(func, y0, t) if torch.is_grad_enabled() else ()
     # (_forward_func: models.ODEBlock hands the forward solve the network's own fused descriptor, as its inference branch does)
     fwd = func if _forward_func is None else _forward_func
+    if linear is not False:
+        lin_plan = _linear_plan(func, params, method, y0, n_points=t.numel()) if torch.is_grad_enabled() else (None, 'gradients are disabled')
+        if linear is True and lin_plan[0] is None:
+            raise ValueError('odeint_discrete(linear=True): the fused linear sweep does not take this call: ' + lin_plan[1])
+        row_plan = None
+        if lower is not False and lin_plan[0] is None:
+            row_plan = _row_plan(func, params, method, y0) if torch.is_grad_enabled() else (None, 'gradients are disabled')
+            if lower is True and row_plan[0] is None:
+                raise ValueError('odeint_discrete(lower=True): the fused row-local sweep does not take this call: ' + row_plan[1])
+        out = _OdeintDiscreteLinear.apply(lin_plan, row_plan, func, fwd, method, options, t, tensor_input, len(params), *params, *ys)
+        return out[0] if tensor_input else tuple(out)
     if lower is not False:
         row_plan = _row_plan(func, params, method, y0) if torch.is_grad_enabled() else (None, 'gradients are disabled')
         if lower is True and row_plan[0] is None:

@@ -78,7 +78,10 @@ class LinearODEFunc(nn.Module):
     models are the MLP above and a convolutional zoo; this is the headline workload's training analogue).
     `weight` is [dim, dim] in [in, out] layout, so that `forward` is one matmul and the fused kernels read it as it is.
     Forward: the whole-call MFMA kernel (`rhs.Linear`); backward under `odeint_adjoint`: the reference's augmented system
-    (adjoint.py:69-105) with its three big products on MFMA kernels instead of autograd over rocBLAS (adjoint._linear_dynamics)."""
+    (adjoint.py:69-105) with its three big products on MFMA kernels instead of autograd over rocBLAS (adjoint._linear_dynamics).
+    Under `odeint_discrete(..., linear='auto')` / `discrete.LINEAR = 'auto'` (ODEBlock(gradient='discrete') reads the latter) the exact
+    fixed-grid gradient is one launch of csrc/mi_ode_discrete_linear.h."""
+    augment_dim = 0               # what ODEBlock asks every odefunc for: the state is never augmented
 
     def __init__(self, dim, bias=True, dtype=torch.float64):
         super(LinearODEFunc, self).__init__()
