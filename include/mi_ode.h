@@ -232,7 +232,8 @@ const char* mi_ode_last_error(void);                      /* thread-local text o
 int64_t mi_ode_reduce_workspace_bytes(void);              /* scratch the stateless reductions need */
 int64_t mi_ode_sizeof(int32_t which);                     /* 0: mi_ode_desc, 1: mi_ode_stats, 2: mi_ode_tableau, 3: mi_ode_rhs,
                                                              5: mi_ode_ctrl_params, 6: mi_ode_adjoint_desc, 7: mi_ode_opq_desc, 8: mi_ode_linadj_desc,
-                                                             9: mi_ode_discrete_desc, 10: mi_ode_discrete_row_desc, 11: mi_ode_discrete_linear_desc
+                                                             9: mi_ode_discrete_desc, 10: mi_ode_discrete_row_desc, 11: mi_ode_discrete_linear_desc,
+                                                             12: mi_ode_discrete_linear_grid_desc
                                                              (lets a foreign-language binding verify its struct layout) */
 
 /* ---- (A) fused engine ---------------------------------------------------------------------- */
@@ -401,7 +402,8 @@ int mi_ode_linadj_profile(mi_ode_linadj_handle h, double* out8);
 /* The reference trains by back-propagating through the solver's own ops (tfdiffeq/fixed_grid.py under the caller's tape); what that
  * returns is the gradient of the discrete map y_{n+1} = y_n + h sum_i b_i f(Y_i), not the continuous adjoint's.  This entry point is that
  * gradient for the time-independent ODEFunc MLP (MI_ODE_RHS_MLP_TANH, fp32, state [batch, dim]) on the default grid (the output times
- * are the grid): with lambda_{n+1} the gradient at y_{n+1}, for i = s .. 1
+ * are the grid; a solve on the grid of options['step_size'] hands it the recomputed grid states and the output gradients placed on
+ * that grid - section A''''''' does both inside the launch for the linear system): with lambda_{n+1} the gradient at y_{n+1}, for i = s .. 1
  *     kbar_i = h b_i lambda_{n+1} + h sum_{j>i} a_ji Ybar_j,   Ybar_i = (df/dy at Y_i)^T kbar_i,   theta_bar += (df/dtheta at Y_i)^T kbar_i,
  * lambda_n = lambda_{n+1} + sum_i Ybar_i + (the output gradient at grid point n).  The stages are recomputed from the stored y_n. */
 typedef struct mi_ode_discrete_desc {
@@ -449,7 +451,8 @@ int mi_ode_discrete_row_sweep(const mi_ode_discrete_row_desc* desc, const mi_ode
 /* ---- (A'''''') the same reverse sweep for the linear system f(y) = y W (+ b) on the matrix cores, ONE launch ------------------------ */
 /* The transpose of the fixed-grid map of MI_ODE_RHS_LINEAR (csrc/mi_ode_discrete_linear.h): Ybar_i = kbar_i W^T, Wbar += Y_i^T kbar_i,
  * bbar += sum_rows kbar_i.  fp32 or fp64, dim <= 128 (smaller dims run zero padded on the 16 / 32 / 64 / 128 wide instantiations), at most
- * 4 stages and 1024 steps.  A persistent grid of at most one workgroup per CU; the parameter gradient is reduced in a fixed order. */
+ * 4 stages and 1024 steps, on the default grid (every grid point an output; a grid of its own: the next section).  A persistent grid of
+ * at most one workgroup per CU; the parameter gradient is reduced in a fixed order. */
 typedef struct mi_ode_discrete_linear_desc {
   int32_t dtype;              /* MI_ODE_F32 / MI_ODE_F64 */
   int32_t dim;                /* 1 .. 128 */
@@ -473,6 +476,44 @@ int mi_ode_discrete_linear_sweep(mi_ode_discrete_linear_handle h, const mi_ode_r
 /* Workgroup 0's clock of the last sweep, microseconds: out3 = {tile sweep (all steps, weight-gradient products included), partial-block
  * store, final hand-off + fold}.  Returns the grid size, or MI_ODE_E_INVALID. */
 int mi_ode_discrete_linear_profile(mi_ode_discrete_linear_handle h, double* out3);
+
+/* ---- (A''''''') the linear reverse sweep for a solve on a grid of its own (options['step_size']), ONE launch, no stored trajectory --- */
+/* The solver walked a grid of n_steps steps and interpolated the n_out requested times linearly inside the step that reaches them
+ * (solvers.py:86-115).  The kernel recomputes the checkpoints of each 16-row tile forward from y0 into a scratch block of its workgroup
+ * (grid x n_steps x 16 x D elements of the state dtype, D the instantiation's width: it does not depend on the batch; at most 1 GiB) and
+ * then runs the reverse sweep of section A'''''' over them, placing the output gradients on the grid as it goes:
+ * gbar_{n_j + 1} += w_j g_j, gbar_{n_j} += (1 - w_j) g_j (the latter only when w_j != 1), output 0 is y0. */
+typedef struct mi_ode_discrete_linear_grid_desc {
+  int32_t dtype;              /* MI_ODE_F32 / MI_ODE_F64 */
+  int32_t dim;                /* 1 .. 128 */
+  int64_t batch;
+  mi_ode_tableau tableau;     /* explicit, at most 3 rows (4 stages): beta = a_ij, c_sol = b */
+  int32_t n_steps;            /* grid steps M, 1 .. 1024 */
+  int32_t n_out;              /* requested times, 2 .. 1025 (the first one is the start of the grid) */
+  int32_t has_bias;           /* 0 / 1: must agree with rhs->b[0] of every sweep */
+  int32_t reserved;
+} mi_ode_discrete_linear_grid_desc;
+typedef struct mi_ode_discrete_linear_grid* mi_ode_discrete_linear_grid_handle;
+/* What can be checked without a device, MI_ODE_E_INVALID or 0: the descriptor (dim < 1 or > 128, n_steps < 1 or > 1024, n_out < 2 or > 1025,
+ * more than 4 stages, a dtype other than fp32 / fp64) and, where the pointers are not NULL, a grid that does not increase, out_step[0] != -1,
+ * an out_step[j >= 1] outside [0, n_steps) or decreasing, a weight outside [0, 1].  create and sweep run it first. */
+int mi_ode_discrete_linear_grid_validate(const mi_ode_discrete_linear_grid_desc* desc, const double* grid_host, const int32_t* out_step,
+                                         const double* out_w);
+/* MI_ODE_E_INVALID also when the checkpoint scratch would exceed 1 GiB (mi_ode_last_error says so). */
+int mi_ode_discrete_linear_grid_create(const mi_ode_discrete_linear_grid_desc* desc, mi_ode_discrete_linear_grid_handle* out);
+int mi_ode_discrete_linear_grid_destroy(mi_ode_discrete_linear_grid_handle h);
+/* grid_host [n_steps + 1]: the solver's grid; out_step [n_out]: the grid step each output was interpolated in (out_step[0] = -1,
+ * non-decreasing); out_w [n_out]: its weight (t_j - t0) / (t1 - t0) in the state dtype, 1 for an exact hit of t1 - all host memory.
+ * y0_dev [batch, dim]; grad_out_dev [n_out, batch, dim]; grad_y0_out_dev [batch, dim]; grad_W_out_dev [dim, dim] in the [in, out] layout
+ * of W; grad_b_out_dev [dim] or NULL.  Step sizes are formed in the state dtype.  Deterministic: the outputs of a step are summed in the
+ * order of j, the parameter gradient in workgroup order.  Blocks until done; returns status bits (>= 0; MI_ODE_ST_SYNC_TIMEOUT: nothing was
+ * committed) or an error (< 0).  stats->n_launches == 1; stats->nfe counts the recomputation and the transposed evaluations. */
+int mi_ode_discrete_linear_grid_sweep(mi_ode_discrete_linear_grid_handle h, const mi_ode_rhs* rhs, const double* grid_host,
+                                      const int32_t* out_step, const double* out_w, const void* y0_dev, const void* grad_out_dev,
+                                      void* grad_y0_out_dev, void* grad_W_out_dev, void* grad_b_out_dev, mi_ode_stats* stats, void* stream);
+/* out3 (may be NULL): as mi_ode_discrete_linear_profile; *scratch_bytes (may be NULL): the checkpoint scratch the handle owns.  Returns
+ * the grid size, or MI_ODE_E_INVALID. */
+int64_t mi_ode_discrete_linear_grid_profile(mi_ode_discrete_linear_grid_handle h, double* out3, int64_t* scratch_bytes);
 
 /* ---- function-level parity surface of the step controller ----------------------------------- */
 /* The scalar tail of one step attempt exactly as the kernels run it (csrc/mi_ode_ctrl_dev.h, ONE device thread per case):

@@ -113,6 +113,12 @@ class DiscreteLinearDesc(C.Structure):
                 ('tableau', Tableau)]
 
 
+class DiscreteLinearGridDesc(C.Structure):
+    """mi_ode_discrete_linear_grid_desc: the same sweep for a solve on a grid of its own (options['step_size']), checkpoints recomputed in the launch."""
+    _fields_ = [('dtype', C.c_int32), ('dim', C.c_int32), ('batch', C.c_int64), ('tableau', Tableau), ('n_steps', C.c_int32), ('n_out', C.c_int32),
+                ('has_bias', C.c_int32), ('reserved', C.c_int32)]
+
+
 DISCRETE_LINEAR_MAX_DIM, DISCRETE_MAX_STEPS = 128, 1024
 
 
@@ -227,6 +233,13 @@ _PROTOS = {
     'mi_ode_discrete_linear_sweep': (C.c_int, [C.c_void_p, C.POINTER(Rhs), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     'mi_ode_discrete_linear_profile': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    'mi_ode_discrete_linear_grid_validate': (C.c_int, [C.POINTER(DiscreteLinearGridDesc), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                                       C.POINTER(C.c_double)]),
+    'mi_ode_discrete_linear_grid_create': (C.c_int, [C.POINTER(DiscreteLinearGridDesc), C.POINTER(C.c_void_p)]),
+    'mi_ode_discrete_linear_grid_destroy': (C.c_int, [C.c_void_p]),
+    'mi_ode_discrete_linear_grid_sweep': (C.c_int, [C.c_void_p, C.POINTER(Rhs), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_discrete_linear_grid_profile': (C.c_int64, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'mi_ode_opq_create': (C.c_int, [C.POINTER(OpqDesc), C.POINTER(C.c_void_p)]),
     'mi_ode_opq_destroy': (C.c_int, [C.c_void_p]),
     'mi_ode_opq_dt_dev': (C.c_void_p, [C.c_void_p]),
@@ -310,7 +323,7 @@ def load():
     if lib.mi_ode_abi_version() != ABI_VERSION:
         raise NativeError('libmi_ode.so ABI version mismatch')
     for which, st in ((0, Desc), (1, Stats), (2, Tableau), (3, Rhs), (5, CtrlParams), (6, AdjointDesc), (7, OpqDesc), (8, LinAdjDesc), (9, DiscreteDesc), (10, DiscreteRowDesc),
-                      (11, DiscreteLinearDesc)):
+                      (11, DiscreteLinearDesc), (12, DiscreteLinearGridDesc)):
         if lib.mi_ode_sizeof(which) != C.sizeof(st):
             raise NativeError('struct layout mismatch for %s: C %d vs ctypes %d'
                               % (st.__name__, lib.mi_ode_sizeof(which), C.sizeof(st)))

@@ -59,6 +59,7 @@ extern "C" int64_t mi_ode_sizeof(int32_t which) {
     case 9: return (int64_t)sizeof(mi_ode_discrete_desc);
     case 10: return (int64_t)sizeof(mi_ode_discrete_row_desc);
     case 11: return (int64_t)sizeof(mi_ode_discrete_linear_desc);
+    case 12: return (int64_t)sizeof(mi_ode_discrete_linear_grid_desc);
     default: return -1;
   }
 }

@@ -23,7 +23,18 @@
 // every workgroup folds its 1 / G share of the entries over the workgroups in index order: no atomics, two calls give identical bits.  A
 // workgroup without tiles stores zeros and takes part in both hand-offs (the first one, right after the slices are loaded, is the residency
 // check of every persistent kernel here).
+//
+// GRID = true (mi_ode_discrete_linear_grid_*): the same sweep for a solve on a grid of its own (options['step_size']) whose outputs were
+// interpolated linearly inside the step that reaches them - WITHOUT a stored trajectory.  Per tile, phase A walks forward from y0 over steps
+// 0 .. M - 2 (S forward evaluations each: k_S is needed here) and stores y_1 .. y_{M-1} into the workgroup's scratch block [M][16][D]; phase B
+// is the reverse loop above with y_n read back from the scratch (y0 for n = 0), and the output gradients placed on the grid as it goes:
+// before the stages of step n  lambda += sum_{j: n_j = n} w_j g_j,  after them  lambda_n += sum (1 - w_j) g_j  of the same outputs (in the
+// order of j; at n = 0 also g_0).  Ownership: a lane stores element i of a row block at row_of(i) * D + col, where row_of(i) = acc_row(lane, i)
+// and col = 16 wave + (lane & 15) are functions of the thread alone (LinCtx::off_of is the same pair with the state's row length) - in
+// phase B the SAME thread reads exactly the addresses it wrote, so program order is all the ordering the scratch needs: no fence, no
+// hand-off, and the next tile of the workgroup reuses the block.  The scratch does not depend on the batch: grid x M x 16 x D elements.
 #pragma once
+#include <type_traits>
 #include "mi_ode_persist.h"
 #include "mi_ode_discrete.h"
 
@@ -46,6 +57,20 @@ struct DiscLinArgs {
   double h[kDiscMaxSteps];     // t[n + 1] - t[n], formed in the state dtype
 };
 
+struct DiscLinGridArgs {       // GRID = true: the argument block of the default-grid kernel (ys, gys, N unused: N = M + 1), then the grid's own
+  DiscLinArgs a;
+  const void* y0;              // [batch, dim]
+  const void* gout;            // [n_out, batch, dim] gradient of the loss with respect to the outputs
+  void* scratch;               // [G][M][16][D] checkpoints of the workgroup's current tile (slot 0 unused: y_0 is y0)
+  int M;                       // grid steps
+  int n_out;
+  int obeg[kDiscMaxSteps + 1]; // outputs j >= 1 assigned to step n: obeg[n] <= j < obeg[n + 1] (non-decreasing assignment)
+  double ow[kDiscMaxSteps + 1];// w_j (state dtype), indexed by output
+};
+
+__device__ __forceinline__ const DiscLinArgs& dl_base(const DiscLinArgs* p) { return *p; }
+__device__ __forceinline__ const DiscLinArgs& dl_base(const DiscLinGridArgs* p) { return p->a; }
+
 __device__ __forceinline__ void dl_store_agent(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void dl_store_agent(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float dl_load_agent(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -54,8 +79,8 @@ __device__ __forceinline__ double dl_load_agent(const double* p) { return __hip_
 template <typename T, int D>
 constexpr size_t discrete_linear_lds_bytes() { return (size_t)(kDiscMaxStages + 2) * LinCtx<T, D>::TILE * sizeof(T); }
 
-template <typename T, int D>
-__global__ __launch_bounds__(D * 4) void k_discrete_linear(const DiscLinArgs* __restrict__ Ap) {
+template <typename T, int D, bool GRID = false>
+__global__ __launch_bounds__(D * 4) void k_discrete_linear(const typename std::conditional<GRID, DiscLinGridArgs, DiscLinArgs>::type* __restrict__ Ap) {
   using CX = LinCtx<T, D>;
   using TR = MfmaTraits<T>;
   using acc_t = typename TR::acc_t;
@@ -63,7 +88,7 @@ __global__ __launch_bounds__(D * 4) void k_discrete_linear(const DiscLinArgs* __
   constexpr int MS = kDiscMaxStages, R_ = CX::R_, LD = CX::LD, TILE = CX::TILE, NB = D / 16, E = D * D + D;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   __shared__ SH sh;
-  const DiscLinArgs& A = *Ap;
+  const DiscLinArgs& A = dl_base(Ap);
   T* const tiles = (T*)smem_raw;                              // [MS + 2][R_][LD]: Y_1 .. Y_S, then the two kbar tiles
   const int dim = A.p.s.dim, S = A.S, N = A.N;
   const long long batch = A.p.s.batch;
@@ -102,20 +127,99 @@ __global__ __launch_bounds__(D * 4) void k_discrete_linear(const DiscLinArgs* __
       unsigned eo[4];
       bool live[4];
       T lm[4], yn[4], gn[4];
+      [[maybe_unused]] unsigned so[4];                        // GRID: this thread's elements inside a slot of the scratch block
+      [[maybe_unused]] T* scr = nullptr;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         eo[i] = fw.off_of(i);
         live[i] = fw.colok && fw.row_of(i) < nr;
-        lm[i] = live[i] ? (gys + (long long)(N - 1) * npl + ebase)[eo[i]] : (T)0;     // lambda_{N-1}: the output gradient at the last grid point
-        yn[i] = live[i] ? (ys + (long long)(N - 2) * npl + ebase)[eo[i]] : (T)0;
-        gn[i] = live[i] ? (gys + (long long)(N - 2) * npl + ebase)[eo[i]] : (T)0;
+      }
+      if constexpr (GRID) {
+        // phase A: the checkpoints y_1 .. y_{M-1} of this tile, forward from y0 (evaluations alternate between tiles 0 and 1: one barrier each)
+        const T* const y0p = (const T*)Ap->y0 + ebase;
+        scr = (T*)Ap->scratch + (long long)blockIdx.x * (long long)(N - 1) * (R_ * D);
+        T yc[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          so[i] = (unsigned)(fw.row_of(i) * D + col);
+          yc[i] = live[i] ? y0p[eo[i]] : (T)0;
+        }
+        fw.s_ys = tiles; fw.cur = 0;
+        for (int n = 0; n + 2 < N; ++n) {
+          const T hs = (T)A.h[n];
+          T kf[MS][4] = {};
+#pragma unroll
+          for (int s = 0; s < MS; ++s) {
+            if (s < S) {
+              T xs[4];
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                T a_ = (T)0;
+#pragma unroll
+                for (int j = 0; j < s; ++j) a_ = j == 0 ? (hs * ca[s][0]) * kf[0][i] : a_ + (hs * ca[s][j]) * kf[j][i];
+                xs[i] = s == 0 ? yc[i] : yc[i] + a_;
+              }
+              fw.rhs_eval(xs, kf[s]);
+            }
+          }
+          T* const sp = scr + (long long)(n + 1) * (R_ * D);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            T a_ = (hs * cb[0]) * kf[0][i];
+#pragma unroll
+            for (int s = 1; s < MS; ++s)
+              if (s < S) a_ = a_ + (hs * cb[s]) * kf[s][i];
+            yc[i] = yc[i] + a_;
+            sp[so[i]] = yc[i];                                // (rows / columns beyond the state stay inside the padded slot; phase B never reads them)
+          }
+        }
+        lds_barrier();                                        // phase B rewrites tiles 0 / 1, which the last chains above read
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          lm[i] = (T)0;                                       // lambda_M is formed from the outputs of the last step, below
+          gn[i] = (T)0;
+          yn[i] = !live[i] ? (T)0 : N - 2 > 0 ? (scr + (long long)(N - 2) * (R_ * D))[so[i]] : y0p[eo[i]];
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          lm[i] = live[i] ? (gys + (long long)(N - 1) * npl + ebase)[eo[i]] : (T)0;     // lambda_{N-1}: the output gradient at the last grid point
+          yn[i] = live[i] ? (ys + (long long)(N - 2) * npl + ebase)[eo[i]] : (T)0;
+          gn[i] = live[i] ? (gys + (long long)(N - 2) * npl + ebase)[eo[i]] : (T)0;
+        }
       }
       for (int n = N - 2; n >= 0; --n) {
         const T hs = (T)A.h[n];
         T y0e[4], g0e[4], k[MS - 1][4] = {}, yb[MS][4] = {};
 #pragma unroll
         for (int i = 0; i < 4; ++i) { y0e[i] = yn[i]; g0e[i] = gn[i]; }
-        if (n > 0) {                                          // the next step's checkpoint and output gradient travel under this step's chains
+        if constexpr (GRID) {
+          if (n > 0) {                                        // the next step's checkpoint travels under this step's chains
+            const T* const yp = n - 1 > 0 ? scr + (long long)(n - 1) * (R_ * D) : (const T*)Ap->y0 + ebase;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) yn[i] = live[i] ? yp[n - 1 > 0 ? so[i] : eo[i]] : (T)0;
+          }
+          // the outputs interpolated inside step n, in the order of j: w_j g_j joins lambda_{n+1}, (1 - w_j) g_j (g0e) lambda_n
+          const T* const go = (const T*)Ap->gout + ebase;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) g0e[i] = (n == 0 && live[i]) ? go[eo[i]] : (T)0;
+          for (int j = Ap->obeg[n]; j < Ap->obeg[n + 1]; ++j) {
+            const T w = (T)Ap->ow[j];
+            const T* const gj = go + (long long)j * npl;
+            if (w != (T)1) {
+              const T w1 = (T)1 - w;
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const T g_ = live[i] ? gj[eo[i]] : (T)0;
+                lm[i] = lm[i] + w * g_;
+                g0e[i] = g0e[i] + w1 * g_;
+              }
+            } else {
+#pragma unroll
+              for (int i = 0; i < 4; ++i) lm[i] = lm[i] + (live[i] ? gj[eo[i]] : (T)0);
+            }
+          }
+        } else if (n > 0) {                                   // the next step's checkpoint and output gradient travel under this step's chains
           const T* const yp = ys + (long long)(n - 1) * npl + ebase;
           const T* const gp = gys + (long long)(n - 1) * npl + ebase;
 #pragma unroll

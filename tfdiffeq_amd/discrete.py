@@ -24,10 +24,14 @@ Four engines:
     parameters trainable: the whole backward, all steps, is ONE launch (csrc/mi_ode_discrete.h);
   * generic sweep   - any `func`, any dtype, tuple states: per step one taped re-evaluation in torch ops and one torch.autograd.grad call.
 
-Scope: euler, midpoint, heun / huen and rk4 (the 3/8 rule) on the default grid (`t` itself) with eps == 0.  Adaptive solves over a
-recorded step sequence, the multistep family and grids of their own (step_size / grid_constructor / eps) are not covered: they raise
-ValueError and name `odeint_adjoint`.
+Scope: euler, midpoint, heun / huen and rk4 (the 3/8 rule) with eps == 0, on the default grid (`t` itself) and - opt-in, `own_grid=True` /
+module default OWN_GRID - on the grid of options['step_size'], whose outputs the solver interpolates linearly inside the step that reaches
+them (solvers.py:86-115).  There the backward recomputes the grid states from y0 (one default-grid solve, cut into segments beyond
+GRID_BYTES), places the output gradients on the grid (_grid_plan) and runs the engines above; the linear system has a kernel mode that
+does all of it in ONE launch without a stored trajectory ('fused linear sweep (own grid)', GRID_KERNEL).  Adaptive solves over a recorded
+step sequence, the multistep family, grid_constructor and eps != 0 are not covered: they raise ValueError and name `odeint_adjoint`.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -52,20 +56,25 @@ LOWER = False                 # default of odeint_discrete(lower=...): False - t
                               # True - raise ValueError where it does not
 LINEAR = False                # default of odeint_discrete(linear=...): False - today's routes; 'auto' - the fused linear sweep where it applies; True -
                               # raise ValueError where it does not
+OWN_GRID = False              # default of odeint_discrete(own_grid=...): False - options['step_size'] raises as before; True - it is accepted
+GRID_BYTES = 1 << 30          # own grid: bound on the recomputed grid states plus their gradients; beyond it the grid is swept in segments
+GRID_KERNEL = True            # own grid, linear system: the one-launch kernel that recomputes its checkpoints (csrc/mi_ode_discrete_linear.h,
+                              # GRID = true); False: the recompute on the grid and the default-grid linear sweep
 ROW_GRID = 0                  # workgroups of the fused row-local sweep; 0: one per 256 trajectories, up to 1024
 _ENGINES = {}
 _LINEAR_ENGINES = {}
 
 
-def check_supported(method, options=None, t=None):
-    """ValueError for everything outside the scope of the discrete gradient, naming the reason and the alternative."""
+def check_supported(method, options=None, t=None, own_grid=False):
+    """ValueError for everything outside the scope of the discrete gradient, naming the reason and the alternative.  own_grid: True
+    accepts options['step_size']."""
     alt = '; use odeint_adjoint (the continuous adjoint) for this call'
     if method not in TABLEAUS:
         raise ValueError('odeint_discrete: method %r is not a fixed-grid Runge-Kutta method (%s): adaptive and multistep solves have no '
                          'fixed discrete map to transpose here%s' % (method, ', '.join(sorted(TABLEAUS)), alt))
     opts = options or {}
     for key in ('step_size', 'grid_constructor'):
-        if opts.get(key) is not None:
+        if opts.get(key) is not None and not (own_grid and key == 'step_size'):
             raise ValueError('odeint_discrete: options[%r] gives the solver a grid of its own and the outputs are interpolated; only the '
                              'default grid (`t` itself) is covered%s' % (key, alt))
     if float(opts.get('eps', 0.0) or 0.0) != 0.0:
@@ -82,6 +91,48 @@ def taped_step(func, tableau, t0, h, y):
         yi = tuple(y_ + sum((h * float(b)) * k[c] for b, k in zip(beta_i, ks) if b != 0.0) for c, y_ in enumerate(y))
         ks.append(func(t0 + float(alpha_i) * h, yi))
     return tuple(y_ + sum((h * float(b)) * k[c] for b, k in zip(tableau.c_sol, ks) if b != 0.0) for c, y_ in enumerate(y))
+
+
+GridPlan = collections.namedtuple('GridPlan', 'grid out_step out_w')
+
+
+def _grid_plan(t, step_size, dtype):
+    """Where a solve with options['step_size'] put its outputs: GridPlan(grid, out_step, out_w).  grid: the solver's own grid, [M + 1] in
+    the state dtype (FixedGridODESolver._grid_constructor_from_step_size on `t` in that dtype); out_step[j]: the grid step n_j whose end
+    is the first t1 >= t[j] (solvers.py:93-100; out_step[0] = -1: output 0 is y0); out_w[j] = (t[j] - t0) / (t1 - t0), formed in the state
+    dtype, exactly 1 where t[j] == t1 (_linear_interp returns y1 itself) and for j = 0.  The output gradients map onto the grid as
+    gbar[n_j + 1] += w_j g_j and gbar[n_j] += (1 - w_j) g_j, the latter only when w_j != 1."""
+    from .solvers import FixedGridODESolver
+    tt = torch.as_tensor(t).detach().cpu().to(dtype)
+    grid = FixedGridODESolver._grid_constructor_from_step_size(None, step_size)(None, None, tt)
+    if not (bool(grid[0] == tt[0]) and bool(grid[-1] == tt[-1])):                         # solvers.py:87
+        raise ValueError('odeint_discrete: the grid of step_size %r does not span t' % (step_size,))
+    out_step, out_w = [-1], [torch.ones((), dtype=dtype)]
+    j, n_out = 1, int(tt.shape[0])
+    for n in range(int(grid.shape[0]) - 1):
+        t0, t1 = grid[n], grid[n + 1]
+        while j < n_out and bool(t1 >= tt[j]):
+            out_step.append(n)
+            out_w.append(torch.ones((), dtype=dtype) if bool(tt[j] == t1) else (tt[j] - t0) / (t1 - t0))
+            j += 1
+    assert j == n_out, 'the grid ends at t[-1]: every output lies inside a step'
+    return GridPlan(grid, out_step, torch.stack(out_w))
+
+
+def _segments(n_steps, point_bytes):
+    """[0, K, 2 K, .., n_steps]: the grid cut so that K + 1 states and as many gradients fit GRID_BYTES (at most 1024 steps each: the
+    fused sweeps take no more).  One segment is the common case."""
+    k = max(1, min(int(n_steps), int(GRID_BYTES) // max(2 * int(point_bytes), 1) - 1, N.DISCRETE_MAX_STEPS))
+    return list(range(0, int(n_steps), k)) + [int(n_steps)]
+
+
+def _segment_points(bounds):
+    """The distinct numbers of grid points of the segments of _segments(), the first segment's first."""
+    out = []
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        if b - a + 1 not in out:
+            out.append(b - a + 1)
+    return tuple(out)
 
 
 def generic_sweep(func, params, ys, t, grad_ys, method):
@@ -295,6 +346,85 @@ def _cached_linear_engine(*key):
     return eng
 
 
+class _FusedLinearGridEngine(object):
+    """Owns one mi_ode_discrete_linear_grid handle: the reverse sweep of `n_steps` grid steps of `method` with `n_out` interpolated outputs
+    for a [batch, dim] state and f(y) = y W (+ b) - checkpoints recomputed from y0 into the handle's scratch, one launch."""
+
+    def __init__(self, batch, dim, has_bias, method, n_steps, n_out, device, dtype):
+        from .solvers import _fill_tableau
+        self.lib = N.load()
+        self.device = torch.device(device)
+        self.dtype = dtype
+        d = N.DiscreteLinearGridDesc()
+        d.dtype, d.dim, d.batch, d.has_bias = N.dtype_code(dtype), int(dim), int(batch), int(bool(has_bias))
+        d.n_steps, d.n_out = int(n_steps), int(n_out)
+        _fill_tableau(d.tableau, TABLEAUS[method], None)
+        self.desc = d
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            N.check(self.lib.mi_ode_discrete_linear_grid_create(C.byref(d), C.byref(h)), 'mi_ode_discrete_linear_grid_create')
+        self.h = h
+        self.batch, self.dim, self.n_steps, self.n_out, self.has_bias = int(batch), int(dim), int(n_steps), int(n_out), bool(has_bias)
+        self.stats = N.Stats()
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.mi_ode_discrete_linear_grid_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def profile(self):
+        """_FusedLinearEngine.profile() plus 'scratch_bytes': the checkpoint scratch the handle owns (grid x n_steps x 16 x D elements)."""
+        out, nbytes = (C.c_double * 3)(), C.c_int64()
+        g = self.lib.mi_ode_discrete_linear_grid_profile(self.h, out, C.byref(nbytes))
+        return {'grid': int(g), 'sweep_us': out[0], 'store_us': out[1], 'fold_us': out[2], 'scratch_bytes': int(nbytes.value)}
+
+    def sweep(self, W, b, gplan, y0, grad_out):
+        """(grad_y0 [batch, dim], grad_W [dim, dim] in W's [in, out] layout, grad_b [dim] or None) from y0 [batch, dim] and the gradient of
+        the loss with respect to the n_out outputs [n_out, batch, dim]; gplan: the GridPlan of the call."""
+        r = N.Rhs()
+        r.kind, r.sign, r.hidden = N.RHS_LINEAR, 1.0, 0
+        W = W.contiguous()
+        r.w[0] = W.data_ptr()
+        if b is not None:
+            b = b.contiguous()
+            r.b[0] = b.data_ptr()
+        y0, grad_out = y0.contiguous(), grad_out.contiguous()
+        g_y0 = torch.empty(self.batch, self.dim, dtype=self.dtype, device=self.device)
+        g_w = torch.empty(self.dim, self.dim, dtype=self.dtype, device=self.device)
+        g_b = torch.empty(self.dim, dtype=self.dtype, device=self.device) if b is not None else None
+        grid = (C.c_double * (self.n_steps + 1))(*[float(v) for v in gplan.grid])
+        step = (C.c_int32 * self.n_out)(*[int(v) for v in gplan.out_step])
+        w = (C.c_double * self.n_out)(*[float(v) for v in gplan.out_w])
+        with torch.cuda.device(self.device):
+            rc = N.check(self.lib.mi_ode_discrete_linear_grid_sweep(self.h, C.byref(r), grid, step, w, y0.data_ptr(), grad_out.data_ptr(), g_y0.data_ptr(),
+                                                                    g_w.data_ptr(), None if g_b is None else g_b.data_ptr(), C.byref(self.stats),
+                                                                    N.stream_ptr(self.device)), 'mi_ode_discrete_linear_grid_sweep')
+        if rc != 0:
+            from .adjoint import HandoffTimeout
+            if rc & N.ST_SYNC_TIMEOUT:
+                raise HandoffTimeout(N.status_message(rc))
+            raise AssertionError(N.status_message(rc))
+        return g_y0, g_w, g_b
+
+
+def _cached_linear_grid_engine(*key):
+    """_cached_linear_engine for the own-grid kernel: the same cache (and the same rule: eviction only drops the cache's reference), the
+    key carries (n_steps, n_out)."""
+    eng = _LINEAR_ENGINES.get(('own grid',) + key)
+    if eng is None:
+        eng = _FusedLinearGridEngine(*key)
+        while len(_LINEAR_ENGINES) >= 4:
+            _LINEAR_ENGINES.pop(next(iter(_LINEAR_ENGINES)))
+        _LINEAR_ENGINES[('own grid',) + key] = eng
+    return eng
+
+
 def _on_device(x):
     return x.is_cuda
 
@@ -302,26 +432,51 @@ def _on_device(x):
 class _LinearPlan(object):
     """What the fused linear sweep of ONE call needs: the parameters themselves (read at the backward, so an in-place optimizer step is
     seen), how the matrix is laid out ('W': [in, out] as the kernel reads it; 'Wt': [out, in], torch.nn.Linear's), where their gradients
-    go among the call's parameters, and the engine."""
+    go among the call's parameters, and the engine.  others: {n_points: engine} for the segments of an own-grid recompute whose length is
+    not the first one's (the shorter last segment) - created at the call with the plan's own, and held by the plan like it."""
 
-    def __init__(self, W, b, how, slots, engine):
-        self.W, self.b, self.how, self.slots, self.engine = W, b, how, slots, engine
+    def __init__(self, W, b, how, slots, engine, key=None, others=None):
+        self.W, self.b, self.how, self.slots, self.engine, self.key, self.others = W, b, how, slots, engine, key, others or {}
+
+    def _engine_for(self, n_points):
+        """The engine of a trajectory of n_points: the plan's own, or the one planned at the call for that length.  (A length nobody
+        planned - a caller of its own - is looked up in the cache, which may create it here.)"""
+        if self.key is None or getattr(self.engine, 'n_points', n_points) == n_points:
+            return self.engine
+        if n_points not in self.others:
+            self.others[n_points] = _cached_linear_engine(*(self.key[:4] + (int(n_points),) + self.key[5:]))
+        return self.others[n_points]
 
     def sweep(self, t, ys, grad_ys, n_params):
         dim = int(ys.shape[-1])
         W = self.W.detach()
+        self.used = self._engine_for(int(ys.shape[0]))       # (whose stats describe this sweep)
+        g_y0, g_w, g_b = self.used.sweep(W if self.how == 'W' else W.t().contiguous(), None if self.b is None else self.b.detach().reshape(-1),
+                                         t, ys.reshape(ys.shape[0], -1, dim), grad_ys.reshape(ys.shape[0], -1, dim))
+        return g_y0, self._place(g_w, g_b, n_params)
+
+    def sweep_grid(self, gplan, y0, grad_out, n_params):
+        """The own-grid kernel (the plan's engine is a _FusedLinearGridEngine): y0 [..., dim], grad_out [n_out, ..., dim]."""
+        dim = int(y0.shape[-1])
+        W = self.W.detach()
         g_y0, g_w, g_b = self.engine.sweep(W if self.how == 'W' else W.t().contiguous(), None if self.b is None else self.b.detach().reshape(-1),
-                                           t, ys.reshape(ys.shape[0], -1, dim), grad_ys.reshape(ys.shape[0], -1, dim))
+                                           gplan, y0.reshape(-1, dim), grad_out.reshape(grad_out.shape[0], -1, dim))
+        return g_y0, self._place(g_w, g_b, n_params)
+
+    def _place(self, g_w, g_b, n_params):
         gp = [None] * n_params
         gp[self.slots[0]] = (g_w if self.how == 'W' else g_w.t().contiguous()).reshape(self.W.shape)
         if self.b is not None:
             gp[self.slots[1]] = g_b.reshape(self.b.shape)
-        return g_y0, gp
+        return gp
 
 
-def _linear_plan(func, params, method, y0, like=None, n_points=None):
+def _linear_plan(func, params, method, y0, like=None, n_points=None, own_grid=None):
     """(_LinearPlan, '') when the fused linear sweep takes this call, else (None, why not).  like: the solution (or any tensor of its
-    shape [N, ...]); without one, n_points is the number of grid points.  Creates (or finds) the engine - at the call, not in backward."""
+    shape [N, ...]); without one, n_points is the number of grid points - or a tuple of them, the distinct segment lengths of an own-grid
+    recompute: the plan's engine is the first one's, the others' are created with it.  own_grid: (n_steps, n_out) of a solve on a grid
+    of its own - the plan then holds the own-grid kernel's engine (the same conditions, n_steps <= 1024 in place of the limit on the
+    points of `t`).  Creates (or finds) every engine - at the call, not in backward."""
     from . import lower as L
     from . import models as M
     if not isinstance(y0, torch.Tensor):
@@ -374,9 +529,18 @@ def _linear_plan(func, params, method, y0, like=None, n_points=None):
         b = ents[1]['t'] if len(ents) > 1 else None
     if dim > N.DISCRETE_LINEAR_MAX_DIM:
         return None, 'dim %d > %d (dims 129 .. 256 are forward-only on the streamed kernels)' % (dim, N.DISCRETE_LINEAR_MAX_DIM)
-    n_points = int(like.shape[0]) if like is not None else int(n_points)
-    if n_points - 1 > N.DISCRETE_MAX_STEPS:
-        return None, 'more than %d steps (%d)' % (N.DISCRETE_MAX_STEPS, n_points - 1)
+    if own_grid is not None:
+        n_steps, n_out = (int(v) for v in own_grid)
+        if n_steps > N.DISCRETE_MAX_STEPS:
+            return None, 'more than %d grid steps (%d)' % (N.DISCRETE_MAX_STEPS, n_steps)
+        if n_out > N.DISCRETE_MAX_STEPS + 1:
+            return None, 'more than %d outputs (%d)' % (N.DISCRETE_MAX_STEPS + 1, n_out)
+    else:
+        lengths = tuple(n_points) if isinstance(n_points, (tuple, list)) else (n_points,)
+        more = tuple(int(v) for v in lengths[1:])
+        n_points = int(like.shape[0]) if like is not None else int(lengths[0])
+        if n_points - 1 > N.DISCRETE_MAX_STEPS:
+            return None, 'more than %d steps (%d)' % (N.DISCRETE_MAX_STEPS, n_points - 1)
     want = [W] + ([] if b is None else [b])
     slots = [next((j for j, p_ in enumerate(params) if p_ is w_), None) for w_ in want]
     if len(params) != len(want) or any(j is None for j in slots):
@@ -386,11 +550,20 @@ def _linear_plan(func, params, method, y0, like=None, n_points=None):
     if not _on_device(y0):
         return None, 'a host tensor'
     batch = y0.numel() // dim
+    others = {}
     try:
-        eng = _cached_linear_engine(batch, dim, b is not None, 'heun' if method == 'huen' else method, n_points, str(y0.device), y0.dtype)
+        if own_grid is not None:
+            key = (batch, dim, b is not None, 'heun' if method == 'huen' else method, n_steps, n_out, str(y0.device), y0.dtype)
+            eng = _cached_linear_grid_engine(*key)
+        else:
+            key = (batch, dim, b is not None, 'heun' if method == 'huen' else method, n_points, str(y0.device), y0.dtype)
+            eng = _cached_linear_engine(*key)
+            for n_ in more:
+                if n_ != n_points:
+                    others[n_] = _cached_linear_engine(*(key[:4] + (n_,) + key[5:]))
     except N.NativeError as e:
         return None, 'the fused engine could not be created (%s)' % e
-    return _LinearPlan(W, b, how, slots, eng), ''
+    return _LinearPlan(W, b, how, slots, eng, key, others), ''
 
 
 class _RowPlan(object):
@@ -522,12 +695,150 @@ def _params_of(func, y0, t):
     return tuple(_graph_leaves(func, y0, t))
 
 
+def _stored_sweep(ctx, t, ans, grad_output):
+    """The reverse sweep over a stored trajectory - `ans`: the states at the grid points `t`, `grad_output`: the gradient of the loss with
+    respect to each - on the first engine that takes it: fused linear, fused row-local, fused mlp, generic.  Returns (tuple of gradients
+    at y0, list of parameter gradients, the last_backward_stats of the sweep)."""
+    func, method, params = ctx.func, ctx.method, ctx.params
+    like = ans[0]
+    n_steps = int(like.shape[0]) - 1
+    lin, lin_why = getattr(ctx, 'linear_plan', None) or (None, '')
+    if lin is not None:
+        from .adjoint import HandoffTimeout
+        try:
+            with torch.no_grad():
+                g_y0, gp = lin.sweep(t.to(like.dtype).double().cpu().numpy(), like, grad_output[0], len(params))
+            stats = {'engine': 'fused linear sweep', 'n_steps': n_steps, 'n_launches': int(lin.used.stats.n_launches),
+                     'why': '', 'method': method, 'forward': ctx.forward_stats}
+            return (g_y0.reshape(like.shape[1:]),), gp, stats
+        except HandoffTimeout as e:                  # the GPU is shared with another persistent kernel: nothing was committed
+            lin_why = 'the fused kernel\'s grid hand-off timed out (%s)' % e
+    row, row_why = getattr(ctx, 'row_plan', None) or (None, '')
+    if row is not None:
+        with torch.no_grad():
+            shape = like.shape
+            g_y0, theta, n_launches = _row_sweep(row, method, t, like.reshape(shape[0], -1, row.dim).contiguous(),
+                                                 grad_output[0].reshape(shape[0], -1, row.dim).contiguous())
+            gp = [None] * len(params)
+            for k, off, n in row.targets:
+                gp[k] = theta[off:off + n].reshape(params[k].shape).to(params[k].dtype)
+        stats = {'engine': 'fused row-local sweep', 'n_steps': n_steps, 'n_launches': n_launches, 'why': '',
+                 'method': method, 'n_params': row.n_params, 'forward': ctx.forward_stats}
+        return (g_y0.reshape(shape[1:]),), gp, stats
+    plan, why = _fused_plan(func, params, method, ctx.tensor_input, like)
+    if row_why:
+        why = 'fused row-local sweep: %s; fused mlp sweep: %s' % (row_why, why)
+    if lin_why:
+        why = 'fused linear sweep: %s; %s' % (lin_why, why if row_why else 'fused mlp sweep: ' + why)
+    if plan is not None:
+        from .adjoint import HandoffTimeout, canonical_to_module_order
+        eng, mlp = plan
+        try:
+            with torch.no_grad():
+                shape = like.shape
+                g_y0, theta = eng.sweep(mlp, t.to(like.dtype).double().cpu().numpy(), like.reshape(shape[0], -1, shape[-1]),
+                                        grad_output[0].reshape(shape[0], -1, shape[-1]))
+                flat = canonical_to_module_order(func, theta)
+                gp = [g.reshape(p.shape).to(p.dtype) for g, p in zip(torch.split(flat, [p.numel() for p in params]), params)]
+            stats = {'engine': 'fused mlp sweep', 'n_steps': n_steps, 'n_launches': int(eng.stats.n_launches),
+                     'why': '', 'method': method, 'forward': ctx.forward_stats}
+            return (g_y0.reshape(shape[1:]),), gp, stats
+        except HandoffTimeout as e:                  # the GPU is shared with another persistent kernel: nothing was committed
+            why = 'the fused kernel\'s grid hand-off timed out (%s)' % e
+    if ctx.tensor_input:
+        def tfunc(t_, y_, _f=func):
+            return (_f(t_, y_[0]),)
+    else:
+        def tfunc(t_, y_, _f=func):
+            return tuple(_f(t_, tuple(y_)))
+    g_y0, gp = generic_sweep(tfunc, params, ans, t, grad_output, method)
+    gp = [None if g is None else g.to(p.dtype) for g, p in zip(gp, params)]
+    stats = {'engine': 'generic sweep', 'n_steps': n_steps, 'n_launches': None, 'why': why, 'method': method, 'forward': ctx.forward_stats}
+    return tuple(g_y0), gp, stats
+
+
+def _own_grid_sweep(ctx, gplan, y0, grad_output):
+    """The backward of a solve on a grid of its own.  The linear system's kernel where the call has its plan (one launch, no stored
+    trajectory); otherwise the grid states are recomputed from y0 - `odeint` on the grid as its default grid, one launch wherever the
+    forward is fused - the output gradients are placed on the grid (_grid_plan) and _stored_sweep runs as on a default grid.  Beyond
+    GRID_BYTES the grid is cut into segments: a forward pass keeps each segment's first state, the backward pass recomputes a segment,
+    sweeps it and adds its lambda to the last gradient of the segment before (every output belongs to the segment of its step, so the
+    boundary point's own gradient is counted once); parameter gradients add up."""
+    method, params = ctx.method, ctx.params
+    grid = gplan.grid
+    n_steps, n_out = int(grid.shape[0]) - 1, len(gplan.out_step)
+    kern, kern_why = getattr(ctx, 'linear_grid_plan', None) or (None, '')
+    if kern is not None:
+        from .adjoint import HandoffTimeout
+        try:
+            with torch.no_grad():
+                g_y0, gp = kern.sweep_grid(gplan, y0[0], grad_output[0], len(params))
+            prof = kern.engine.profile()
+            # (n_segments 0, recompute_launches 0: the kernel recomputes inside its own launch - no grid state is ever stored)
+            stats = {'engine': 'fused linear sweep (own grid)', 'n_steps': n_steps, 'n_launches': int(kern.engine.stats.n_launches), 'why': '',
+                     'method': method, 'forward': ctx.forward_stats,
+                     'own_grid': {'n_grid_steps': n_steps, 'n_segments': 0, 'recompute_launches': 0, 'grid': prof['grid'],
+                                  'scratch_bytes': prof['scratch_bytes']}}
+            return (g_y0.reshape(y0[0].shape),), gp, stats
+        except HandoffTimeout as e:                  # nothing was committed: the recompute on the grid takes the call ...
+            kern_why = 'the fused kernel\'s grid hand-off timed out (%s)' % e
+            # ... on the default-grid linear sweep, which was not planned while the kernel's plan stood (a refusal goes on to the
+            # other engines with its reason, as it would have at the call)
+            seg = _segments(n_steps, sum(y.numel() * y.element_size() for y in y0))
+            ctx.linear_plan = _linear_plan(ctx.func, params, method, y0[0], n_points=_segment_points(seg))
+    w_hi = [float(v) for v in gplan.out_w]
+    w_lo = [float(v) for v in (torch.ones_like(gplan.out_w) - gplan.out_w)]              # 1 - w_j, formed in the state dtype
+    bounds = _segments(n_steps, sum(y.numel() * y.element_size() for y in y0))
+    n_seg = len(bounds) - 1
+    launches = 0
+
+    def solve(start, a, b):
+        with torch.no_grad():
+            out = odeint(ctx.fwd, start[0] if ctx.tensor_input else tuple(start), grid[a:b + 1], method=method)
+        return (out,) if isinstance(out, torch.Tensor) else tuple(out)
+    starts = [tuple(y.detach() for y in y0)]
+    for s in range(n_seg - 1):                       # forward: only each segment's first state is kept
+        starts.append(tuple(o[-1].clone() for o in solve(starts[-1], bounds[s], bounds[s + 1])))
+        launches += 1
+    lam, gp_sum, n_launches, stats = None, [None] * len(params), 0, None
+    for s in range(n_seg - 1, -1, -1):
+        a, b = bounds[s], bounds[s + 1]
+        ys = solve(starts[s], a, b)
+        launches += 1
+        with torch.no_grad():
+            gbar = tuple(torch.zeros_like(c) for c in ys)
+            for j in range(n_out):                   # in the order of j: two calls give identical bits
+                n = gplan.out_step[j]
+                if not (a <= n < b or (j == 0 and a == 0)):
+                    continue
+                for gb_, g_ in zip(gbar, grad_output):
+                    if w_hi[j] == 1.0:
+                        gb_[n + 1 - a] += g_[j]
+                    else:
+                        gb_[n + 1 - a] += w_hi[j] * g_[j]
+                        gb_[n - a] += w_lo[j] * g_[j]
+            if lam is not None:
+                for gb_, l_ in zip(gbar, lam):
+                    gb_[b - a] += l_
+        lam, gp, stats = _stored_sweep(ctx, grid[a:b + 1], ys, gbar)
+        del ys, gbar
+        for i, g in enumerate(gp):
+            if g is not None:
+                gp_sum[i] = g if gp_sum[i] is None else gp_sum[i] + g
+        n_launches = None if n_launches is None or stats['n_launches'] is None else n_launches + stats['n_launches']
+    stats = dict(stats, n_steps=n_steps, n_launches=n_launches)
+    if kern_why:
+        stats['why'] = 'fused linear sweep (own grid): %s%s' % (kern_why, '; ' + stats['why'] if stats['why'] else '')
+    stats['own_grid'] = {'n_grid_steps': n_steps, 'n_segments': n_seg, 'recompute_launches': launches}
+    return lam, gp_sum, stats
+
+
 class _OdeintDiscrete(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, func, fwd, method, options, t, tensor_input, n_params, *args):
         params, y0 = args[:n_params], args[n_params:]
-        ctx.func, ctx.method, ctx.tensor_input, ctx.n_params = func, method, tensor_input, n_params
+        ctx.func, ctx.fwd, ctx.method, ctx.tensor_input, ctx.n_params = func, fwd, method, tensor_input, n_params
         ctx.params = params
         with torch.no_grad():
             ans = odeint(fwd, y0[0] if tensor_input else tuple(y0), t, method=method, options=options)
@@ -535,70 +846,27 @@ class _OdeintDiscrete(torch.autograd.Function):
         if isinstance(ans, torch.Tensor):
             ans = (ans,)
         ctx.t = t
-        ctx.save_for_backward(*ans)
+        step_size = (options or {}).get('step_size')
+        gplan = getattr(ctx, 'grid_plan', None)          # (_OdeintDiscreteLinearGrid has formed it for its planning)
+        ctx.grid_plan = _grid_plan(t, step_size, ans[0].dtype) if gplan is None and step_size is not None else gplan
+        if ctx.grid_plan is None:
+            ctx.save_for_backward(*ans)
+        else:                                            # (y0 is an input: keeping it costs nothing; the grid states are recomputed)
+            ctx.save_for_backward(*(tuple(ans) + tuple(y0)))
         return tuple(ans)
 
     @staticmethod
     def backward(ctx, *grad_output):
-        func, method, params = ctx.func, ctx.method, ctx.params
-        ans = ctx.saved_tensors
-        like = ans[0]
-        t = ctx.t.detach()
-        grad_output = tuple(g if g is not None else torch.zeros_like(a) for g, a in zip(grad_output, ans))
-        n_steps = int(like.shape[0]) - 1
-        lin, lin_why = getattr(ctx, 'linear_plan', None) or (None, '')
-        if lin is not None:
-            from .adjoint import HandoffTimeout
-            try:
-                with torch.no_grad():
-                    g_y0, gp = lin.sweep(t.to(like.dtype).double().cpu().numpy(), like, grad_output[0], len(params))
-                odeint_discrete.last_backward_stats = {'engine': 'fused linear sweep', 'n_steps': n_steps, 'n_launches': int(lin.engine.stats.n_launches),
-                                                       'why': '', 'method': method, 'forward': ctx.forward_stats}
-                return (None,) * 7 + tuple(gp) + (g_y0.reshape(like.shape[1:]),)
-            except HandoffTimeout as e:                  # the GPU is shared with another persistent kernel: nothing was committed
-                lin_why = 'the fused kernel\'s grid hand-off timed out (%s)' % e
-        row, row_why = getattr(ctx, 'row_plan', None) or (None, '')
-        if row is not None:
-            with torch.no_grad():
-                shape = like.shape
-                g_y0, theta, n_launches = _row_sweep(row, method, t, like.reshape(shape[0], -1, row.dim).contiguous(),
-                                                     grad_output[0].reshape(shape[0], -1, row.dim).contiguous())
-                gp = [None] * len(params)
-                for k, off, n in row.targets:
-                    gp[k] = theta[off:off + n].reshape(params[k].shape).to(params[k].dtype)
-            odeint_discrete.last_backward_stats = {'engine': 'fused row-local sweep', 'n_steps': n_steps, 'n_launches': n_launches, 'why': '',
-                                                   'method': method, 'n_params': row.n_params, 'forward': ctx.forward_stats}
-            return (None,) * 7 + tuple(gp) + (g_y0.reshape(shape[1:]),)
-        plan, why = _fused_plan(func, params, method, ctx.tensor_input, like)
-        if row_why:
-            why = 'fused row-local sweep: %s; fused mlp sweep: %s' % (row_why, why)
-        if lin_why:
-            why = 'fused linear sweep: %s; %s' % (lin_why, why if row_why else 'fused mlp sweep: ' + why)
-        if plan is not None:
-            from .adjoint import HandoffTimeout, canonical_to_module_order
-            eng, mlp = plan
-            try:
-                with torch.no_grad():
-                    shape = like.shape
-                    g_y0, theta = eng.sweep(mlp, t.to(like.dtype).double().cpu().numpy(), like.reshape(shape[0], -1, shape[-1]),
-                                            grad_output[0].reshape(shape[0], -1, shape[-1]))
-                    flat = canonical_to_module_order(func, theta)
-                    gp = [g.reshape(p.shape).to(p.dtype) for g, p in zip(torch.split(flat, [p.numel() for p in params]), params)]
-                odeint_discrete.last_backward_stats = {'engine': 'fused mlp sweep', 'n_steps': n_steps, 'n_launches': int(eng.stats.n_launches),
-                                                       'why': '', 'method': method, 'forward': ctx.forward_stats}
-                return (None,) * 7 + tuple(gp) + (g_y0.reshape(shape[1:]),)
-            except HandoffTimeout as e:                  # the GPU is shared with another persistent kernel: nothing was committed
-                why = 'the fused kernel\'s grid hand-off timed out (%s)' % e
-        if ctx.tensor_input:
-            def tfunc(t_, y_, _f=func):
-                return (_f(t_, y_[0]),)
+        if ctx.grid_plan is None:
+            ans = ctx.saved_tensors
         else:
-            def tfunc(t_, y_, _f=func):
-                return tuple(_f(t_, tuple(y_)))
-        g_y0, gp = generic_sweep(tfunc, params, ans, t, grad_output, method)
-        gp = [None if g is None else g.to(p.dtype) for g, p in zip(gp, params)]
-        odeint_discrete.last_backward_stats = {'engine': 'generic sweep', 'n_steps': n_steps, 'n_launches': None, 'why': why, 'method': method,
-                                               'forward': ctx.forward_stats}
+            ans, y0 = ctx.saved_tensors[:len(grad_output)], ctx.saved_tensors[len(grad_output):]
+        grad_output = tuple(g if g is not None else torch.zeros_like(a) for g, a in zip(grad_output, ans))
+        if ctx.grid_plan is None:
+            g_y0, gp, stats = _stored_sweep(ctx, ctx.t.detach(), ans, grad_output)
+        else:
+            g_y0, gp, stats = _own_grid_sweep(ctx, ctx.grid_plan, y0, grad_output)
+        odeint_discrete.last_backward_stats = stats
         return (None,) * 7 + tuple(gp) + tuple(g_y0)
 
 
@@ -628,15 +896,36 @@ class _OdeintDiscreteLinear(torch.autograd.Function):
         return (None, None) + _OdeintDiscrete.backward(ctx, *grad_output)
 
 
-def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=None, _forward_func=None):
+class _OdeintDiscreteLinearGrid(torch.autograd.Function):
+    """_OdeintDiscreteLinear with the call's GridPlan and the outcome of the own-grid kernel's planning in front of its arguments."""
+
+    @staticmethod
+    def forward(ctx, grid_plan, linear_grid_plan, linear_plan, row_plan, *args):
+        ctx.grid_plan, ctx.linear_grid_plan, ctx.linear_plan, ctx.row_plan = grid_plan, linear_grid_plan, linear_plan, row_plan
+        return _OdeintDiscrete.forward(ctx, *args)
+
+    @staticmethod
+    def backward(ctx, *grad_output):
+        return (None, None, None, None) + _OdeintDiscrete.backward(ctx, *grad_output)
+
+
+def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=None, own_grid=None, _forward_func=None):
     """`odeint(func, y0, t, method=method, options=options)` - same values, same engine - whose result is differentiable with respect to
     y0 and func's trainable tensors, with the gradient of the DISCRETE map the solver computed (what back-propagating through the
     reference's solver gives), not the continuous adjoint's.
 
-    method: 'euler', 'midpoint', 'heun' / 'huen' or 'rk4' (the 3/8 rule), on the default grid (`t` itself) with eps == 0.  Anything else -
-    adaptive and multistep methods, the step_size / grid_constructor / eps options, a `t` that requires grad - raises ValueError and
-    names `odeint_adjoint`.  Adaptive solves over a recorded step sequence are out of scope.  Tensor and tuple states are accepted;
+    method: 'euler', 'midpoint', 'heun' / 'huen' or 'rk4' (the 3/8 rule) with eps == 0, on the default grid (`t` itself) or, with
+    own_grid=True, on the grid of options['step_size'].  Anything else - adaptive and multistep methods, the grid_constructor / eps options,
+    step_size without own_grid, a `t` that requires grad - raises ValueError and names `odeint_adjoint`.  Adaptive solves over a recorded step
+    sequence are out of scope.  Tensor and tuple states are accepted;
     parameters are found as odeint / odeint_adjoint find them (module parameters; the grad-requiring leaves of a plain callable).
+    own_grid: None - the module default `discrete.OWN_GRID` (False); False - options['step_size'] raises; True - it is accepted: the forward is
+    the plain odeint call (one launch on the grid-walking kernel, len(t) outputs), the backward recomputes the grid states from y0 and runs
+    the engines below on them (in segments beyond `discrete.GRID_BYTES`); with linear='auto' / True the linear system's whole backward is ONE
+    launch that recomputes its own checkpoints ('fused linear sweep (own grid)', up to 1024 grid steps; `discrete.GRID_KERNEL = False` turns it
+    off).  last_backward_stats then has 'own_grid': {'n_grid_steps', 'n_segments', 'recompute_launches'} and 'n_steps' counts grid steps;
+    the own-grid kernel reports n_segments 0 and recompute_launches 0 - it recomputes inside its one launch and stores no grid state - and
+    adds 'grid' (workgroups) and 'scratch_bytes' (its checkpoint scratch: grid x n_steps x 16 x D elements, independent of the batch).
     lower: None - the module default `discrete.LOWER` (False); False - the routes above; 'auto' - a callable the tracer lowers to a row-local
     program runs its whole backward in one launch (generated vjp, csrc/mi_ode_discrete_row.h), anything else falls to the routes above
     with the reason in last_backward_stats['why']; True - ValueError with that reason, here at the call.
@@ -644,9 +933,13 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=
     callable the tracer puts in the 'linear' family: `y @ W`, `y @ W + b`, torch.nn.Linear(d, d)), float32 / float64, dim <= 128, runs its
     whole backward in one launch on the matrix cores (csrc/mi_ode_discrete_linear.h), anything else falls to the routes above with the
     reason in last_backward_stats['why']; True - ValueError with that reason, here at the call.
-    `odeint_discrete.last_backward_stats`: {'engine': 'fused linear sweep' | 'fused row-local sweep' | 'fused mlp sweep' | 'generic sweep', 'n_steps',
+    `odeint_discrete.last_backward_stats`: {'engine': 'fused linear sweep' | 'fused linear sweep (own grid)' | 'fused row-local sweep' |
+    'fused mlp sweep' | 'generic sweep', 'n_steps',
     'n_launches', 'why'} of the last backward ('why': the reason the fused kernels were not used)."""
-    check_supported(method, options, t)
+    own_grid = OWN_GRID if own_grid is None else own_grid
+    if own_grid not in (False, True):
+        raise ValueError('odeint_discrete: own_grid must be False or True, not %r' % (own_grid,))
+    check_supported(method, options, t, own_grid=own_grid)
     lower = LOWER if lower is None else lower
     if lower not in (False, True, 'auto'):
         raise ValueError("odeint_discrete: lower must be False, True or 'auto', not %r" % (lower,))
@@ -661,6 +954,29 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=
     params = _params_of(func, y0, t) if torch.is_grad_enabled() else ()
     # (_forward_func: models.ODEBlock hands the forward solve the network's own fused descriptor, as its inference branch does)
     fwd = func if _forward_func is None else _forward_func
+    step_size = (options or {}).get('step_size')
+    if linear is not False and step_size is not None:
+        # a grid of its own: the kernel that recomputes its checkpoints, else the default-grid sweep over a recompute (planned for the
+        # segment length the backward will use)
+        dtype = y0.dtype if tensor_input else ys[0].dtype
+        gplan = _grid_plan(t, step_size, dtype)
+        n_grid_steps = int(gplan.grid.shape[0]) - 1
+        off = (None, 'gradients are disabled')
+        kern_plan = off if not torch.is_grad_enabled() else (None, 'discrete.GRID_KERNEL is False') if not GRID_KERNEL else \
+            _linear_plan(func, params, method, y0, own_grid=(n_grid_steps, len(gplan.out_step)))
+        lin_plan = (None, '')
+        if kern_plan[0] is None:
+            seg = _segments(n_grid_steps, sum(y_.numel() * y_.element_size() for y_ in ys))
+            lin_plan = off if not torch.is_grad_enabled() else _linear_plan(func, params, method, y0, n_points=_segment_points(seg))
+            if linear is True and lin_plan[0] is None:
+                raise ValueError('odeint_discrete(linear=True): the fused linear sweep does not take this call: ' + lin_plan[1])
+        row_plan = None
+        if lower is not False and kern_plan[0] is None and lin_plan[0] is None:
+            row_plan = _row_plan(func, params, method, y0) if torch.is_grad_enabled() else (None, 'gradients are disabled')
+            if lower is True and row_plan[0] is None:
+                raise ValueError('odeint_discrete(lower=True): the fused row-local sweep does not take this call: ' + row_plan[1])
+        out = _OdeintDiscreteLinearGrid.apply(gplan, kern_plan, lin_plan, row_plan, func, fwd, method, options, t, tensor_input, len(params), *params, *ys)
+        return out[0] if tensor_input else tuple(out)
     if linear is not False:
         lin_plan = _linear_plan(func, params, method, y0, n_points=t.numel()) if torch.is_grad_enabled() else (None, 'gradients are disabled')
         if linear is True and lin_plan[0] is None:

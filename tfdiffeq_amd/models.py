@@ -80,7 +80,8 @@ class LinearODEFunc(nn.Module):
     Forward: the whole-call MFMA kernel (`rhs.Linear`); backward under `odeint_adjoint`: the reference's augmented system
     (adjoint.py:69-105) with its three big products on MFMA kernels instead of autograd over rocBLAS (adjoint._linear_dynamics).
     Under `odeint_discrete(..., linear='auto')` / `discrete.LINEAR = 'auto'` (ODEBlock(gradient='discrete') reads the latter) the exact
-    fixed-grid gradient is one launch of csrc/mi_ode_discrete_linear.h."""
+    fixed-grid gradient is one launch of csrc/mi_ode_discrete_linear.h - also on the grid of options['step_size'] (discrete.OWN_GRID = True),
+    where the kernel recomputes its checkpoints instead of reading a stored trajectory."""
     augment_dim = 0               # what ODEBlock asks every odefunc for: the state is never augmented
 
     def __init__(self, dim, bias=True, dtype=torch.float64):
