@@ -401,11 +401,14 @@ int mi_ode_linadj_profile(mi_ode_linadj_handle h, double* out8);
 /* ---- (A'''') exact gradient of a fixed-grid solve: the reverse sweep of the discrete map, ONE launch --------------------- */
 /* The reference trains by back-propagating through the solver's own ops (tfdiffeq/fixed_grid.py under the caller's tape); what that
  * returns is the gradient of the discrete map y_{n+1} = y_n + h sum_i b_i f(Y_i), not the continuous adjoint's.  This entry point is that
- * gradient for the time-independent ODEFunc MLP (MI_ODE_RHS_MLP_TANH, fp32, state [batch, dim]) on the default grid (the output times
+ * gradient for the ODEFunc MLP (MI_ODE_RHS_MLP_TANH, fp32, state [batch, dim]; time independent, or time dependent - the first layer
+ * sees concat([t, x]), mi_ode_discrete_create_td) on the default grid (the output times
  * are the grid; a solve on the grid of options['step_size'] hands it the recomputed grid states and the output gradients placed on
  * that grid - section A''''''' does both inside the launch for the linear system): with lambda_{n+1} the gradient at y_{n+1}, for i = s .. 1
  *     kbar_i = h b_i lambda_{n+1} + h sum_{j>i} a_ji Ybar_j,   Ybar_i = (df/dy at Y_i)^T kbar_i,   theta_bar += (df/dtheta at Y_i)^T kbar_i,
- * lambda_n = lambda_{n+1} + sum_i Ybar_i + (the output gradient at grid point n).  The stages are recomputed from the stored y_n. */
+ * lambda_n = lambda_{n+1} + sum_i Ybar_i + (the output gradient at grid point n).  The stages are recomputed from the stored y_n, the
+ * time-dependent network's at the times the forward step functions form in the state dtype (t_n, t_n + h / 2, t_n + h, t_n + h / 3,
+ * t_n + h 2 / 3): the actual, decreasing times on a decreasing grid. */
 typedef struct mi_ode_discrete_desc {
   int64_t batch;
   int32_t dim, hidden;
@@ -414,13 +417,23 @@ typedef struct mi_ode_discrete_desc {
   int32_t chunk_tiles;        /* 32-row tiles of a workgroup that share one weight-gradient pass; 0: all of them */
 } mi_ode_discrete_desc;
 typedef struct mi_ode_discrete* mi_ode_discrete_handle;
-int mi_ode_discrete_create(const mi_ode_discrete_desc* desc, mi_ode_discrete_handle* out);
+int mi_ode_discrete_create(const mi_ode_discrete_desc* desc, mi_ode_discrete_handle* out);      /* the time-independent network */
+/* time_dependent: 0 - as mi_ode_discrete_create; 1 - the handle is sized for the time-dependent network (rhs->scalars[1] != 0, W1 is
+ * [1 + dim, hidden] with the row of t first): `hidden` more parameters.  The sizes are fixed at creation, hence the flag here.
+ * Stage i is evaluated at t_n + (h p) / q with alpha_i = p / q, q the smallest of 1, 2, 3 that makes p an integer - the divisions the
+ * forward step functions perform for euler, midpoint, heun and the 3/8 rule (h / 2, h / 3, (h 2) / 3), so the recomputed stage is the
+ * stage the forward ran.  Any other alpha is taken as t_n + h alpha (rounded to the state dtype once): exact to rounding, not bitwise
+ * the time of a forward that divides differently. */
+int mi_ode_discrete_create_td(const mi_ode_discrete_desc* desc, int32_t time_dependent, mi_ode_discrete_handle* out);
 int mi_ode_discrete_destroy(mi_ode_discrete_handle h);
 int64_t mi_ode_discrete_num_params(mi_ode_discrete_handle h);
-/* t_host: the N grid times (host).  ys_dev: the forward solution [N, batch, dim]; grad_ys_dev: the gradient of the loss with respect
- * to it, same shape; grad_y0_out_dev [batch, dim]; grad_theta_out_dev: mi_ode_discrete_num_params() entries in the canonical order of
- * (A').  All device memory, fp32.  rhs: the weights (sign is ignored).  Deterministic: two calls give identical bits.  Blocks until
- * done; returns status bits (>= 0) or an error (< 0).  stats->n_launches == 1. */
+/* t_host: the N grid times (host): their differences in the state dtype are the step sizes, and the times themselves are what the
+ * time-dependent network is evaluated at.  ys_dev: the forward solution [N, batch, dim]; grad_ys_dev: the gradient of the loss with
+ * respect to it, same shape; grad_y0_out_dev [batch, dim]; grad_theta_out_dev: mi_ode_discrete_num_params() entries in the canonical
+ * order of (A'): (w_t [hidden] when time dependent - row 0 of W1,) W1 [dim][hidden], b1, W2, b2, W3, b3, weights [in, out].  All device
+ * memory, fp32.  rhs: the weights (sign is ignored); MI_ODE_E_INVALID when rhs->scalars[1] disagrees with the handle's flag.
+ * Deterministic: two calls give identical bits.  Blocks until done; returns status bits (>= 0) or an error (< 0).
+ * stats->n_launches == 1. */
 int mi_ode_discrete_sweep(mi_ode_discrete_handle h, const mi_ode_rhs* rhs, const double* t_host, const void* ys_dev,
                           const void* grad_ys_dev, void* grad_y0_out_dev, void* grad_theta_out_dev, mi_ode_stats* stats, void* stream);
 

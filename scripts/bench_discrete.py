@@ -11,7 +11,11 @@ One process, in-run HIP events, min / median / max over the timed steps after th
 fraction of the fp32 matrix peak (157.3 TFLOP/s) follows from its own multiply-add count: forward recompute, backward data and weight
 gradients, 3 x (d h + h h + h d) per row, stage and step.
 
-usage: python scripts/bench_discrete.py [--steps 20] [--warmup 5] [--chunks 0,1] [--out profiles/discrete_bench.txt] [--only fused]
+--time-dependent: ODEFunc(time_dependent=True) - the first layer sees concat([t, x]); the fused kernel then adds the stage time's bias
+shift and the gradient of w_t (the multiply-add count above is unchanged: w_t is one more bias-like sum).
+
+usage: python scripts/bench_discrete.py [--steps 20] [--warmup 5] [--chunks 0,1] [--out FILE] [--only fused] [--time-dependent]
+(--out defaults to profiles/discrete_bench.txt, and to profiles/discrete_td_bench.txt with --time-dependent)
 """
 import argparse
 import os
@@ -50,13 +54,16 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--chunks', default='0,1', help='tiles per weight-gradient pass of the fused kernel to compare (0: all of a workgroup\'s)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'discrete_bench.txt'))
+    ap.add_argument('--out', default='', help='default: profiles/discrete_bench.txt, profiles/discrete_td_bench.txt with --time-dependent')
     ap.add_argument('--only', default='', help='comma-separated subset of taped,generic,fused')
+    ap.add_argument('--time-dependent', action='store_true', help='the time-dependent network (fc1 sees concat([t, x]))')
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, 'profiles', 'discrete_td_bench.txt' if args.time_dependent else 'discrete_bench.txt')
     only = set(filter(None, args.only.split(',')))
     dev = torch.device('cuda:0')
-    lines = ['# scripts/bench_discrete.py --steps %d --warmup %d: %s, 64-128-128-64 tanh float32; ms per training step (min / median / max)'
-             % (args.steps, args.warmup, torch.cuda.get_device_name(0))]
+    lines = ['# scripts/bench_discrete.py --steps %d --warmup %d%s: %s, 64-128-128-64 tanh float32%s; ms per training step (min / median / max)'
+             % (args.steps, args.warmup, ' --time-dependent' if args.time_dependent else '', torch.cuda.get_device_name(0),
+                ', time dependent' if args.time_dependent else '')]
 
     def say(s):
         print(s, flush=True)
@@ -64,7 +71,7 @@ def main():
 
     for batch in (32768, 4096):
         torch.manual_seed(0)
-        func = models.ODEFunc(DIM, HID, non_linearity='tanh').to(dev)
+        func = models.ODEFunc(DIM, HID, time_dependent=args.time_dependent, non_linearity='tanh').to(dev)
         x = torch.randn(batch, DIM, device=dev)
         w = torch.randn(batch, DIM, device=dev)
         for method, n in (('rk4', 5), ('rk4', 21), ('euler', 2)):
@@ -102,7 +109,7 @@ def main():
                 st = odeint_discrete.last_backward_stats
                 assert st['engine'] == 'fused mlp sweep' and st['n_launches'] == 1, st
                 # the kernel alone: the engine's blocking sweep call on the last forward solution
-                eng = discrete._cached_engine(batch, DIM, HID, method, n, str(dev), chunk)
+                eng = discrete._cached_engine(batch, DIM, HID, method, n, str(dev), chunk, args.time_dependent)
                 with torch.no_grad():
                     ys = block(x, eval_times=t).contiguous()
                 gys = torch.zeros_like(ys)

@@ -222,6 +222,7 @@ _PROTOS = {
                                         C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(Stats), C.c_void_p]),
     'mi_ode_linadj_profile': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'mi_ode_discrete_create': (C.c_int, [C.POINTER(DiscreteDesc), C.POINTER(C.c_void_p)]),
+    'mi_ode_discrete_create_td': (C.c_int, [C.POINTER(DiscreteDesc), C.c_int32, C.POINTER(C.c_void_p)]),
     'mi_ode_discrete_destroy': (C.c_int, [C.c_void_p]),
     'mi_ode_discrete_num_params': (C.c_int64, [C.c_void_p]),
     'mi_ode_discrete_sweep': (C.c_int, [C.c_void_p, C.POINTER(Rhs), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1,7 +1,7 @@
 // The exact gradient of a fixed-grid Runge-Kutta solve of the ODEFunc MLP (csrc/mi_ode_adjoint.h: same network, same operand layouts),
-// fp32, time independent: the TRANSPOSE of the discrete map the forward kernel computed, all steps in ONE launch.
+// fp32, time dependent or not: the TRANSPOSE of the discrete map the forward kernel computed, all steps in ONE launch.
 //
-// Forward step n (fixed_grid.py / rk_common.py:73-81):  Y_i = y_n + h sum_{j<i} a_ij k_j,  k_i = f(Y_i),  y_{n+1} = y_n + h sum_i b_i k_i.
+// Forward step n (fixed_grid.py / rk_common.py:73-81):  Y_i = y_n + h sum_{j<i} a_ij k_j,  k_i = f(t_i, Y_i),  y_{n+1} = y_n + h sum_i b_i k_i.
 // With lambda_{n+1} = dL/dy_{n+1} the reverse sweep runs, for i = s .. 1,
 //     kbar_i = h b_i lambda_{n+1} + h sum_{j>i} a_ji Ybar_j,     Ybar_i = (df/dy at Y_i)^T kbar_i,     theta_bar += (df/dtheta at Y_i)^T kbar_i
 // and lambda_n = lambda_{n+1} + sum_i Ybar_i + gbar_n (gbar_n: the caller's gradient of the output at grid point n).
@@ -19,6 +19,14 @@
 // (smallest scratch).  At the end ONE grid hand-off, then every workgroup folds its 1/G slice of theta_bar over the workgroups in a fixed
 // order (adj_slice): no atomics, two runs give identical bits.  (A first hand-off right after the weights are staged is the residency
 // check of every persistent kernel here.)
+// Time-dependent network (a.td, dense_odenet.py:79-84): stage i of step n sees t_i = t_n + (h tn_i) / td_i in the state dtype - t_n + h / 2,
+// t_n + h, t_n + h / 3, t_n + h 2 / 3: what fixed_grid.py and k_fixed_mlp form - as the bias shift t_i w_t of the first layer.  w_t does
+// not multiply y, so the backward-data passes are what they were; its gradient is sum t_i (column sum of G1), which adj_wgrad_pass carries
+// in st[] from the stage times of its pass list.  The stage times are formed once per step (disc_prepare), for the pass list and for the
+// tile pass, so the weight applied to a column sum is the time its stage was evaluated at.  The tile pass has no register to spare (248
+// VGPRs, 102 SGPRs before this): the bias shifts t_i w_t of the step's stages sit behind the dynamic LDS segment of AdjGeom (DiscLds:
+// 4 x HP floats, zero for the time-independent network) and layer 1 reads its column's where it adds the bias - one transient register.
+// theta_bar then starts with w_t [hidden].
 #pragma once
 #include "mi_ode_adjoint.h"
 
@@ -45,18 +53,40 @@ struct DiscArgs {
   int chunk;                   // tiles per weight-gradient pass
   float ha[kDiscMaxStages][kDiscMaxStages];   // a_ij (row i, j < i)
   float hb[kDiscMaxStages];
+  float tn[kDiscMaxStages], tdn[kDiscMaxStages];   // stage i is evaluated at t[n] + (h tn[i]) / tdn[i] (stage 0 at t[n])
   float h[kDiscMaxSteps];      // t[n + 1] - t[n] in the state dtype
+  float t0[kDiscMaxSteps];     // t[n] in the state dtype (time-dependent network)
 };
+
+// What the discrete kernel keeps behind AdjGeom's dynamic LDS segment: tw[stage][HP] = t_stage w_t[column] of the current step (zero in
+// the padding, all zero for the time-independent network).
+template <int DP, int HP>
+struct DiscLds {
+  static constexpr int OFF_TW = (int)(AdjGeom<DP, HP>::lds_bytes() / sizeof(float));
+  static constexpr size_t lds_bytes() { return (size_t)(OFF_TW + kDiscMaxStages * HP) * sizeof(float); }
+};
+
+// The times the network sees at the stages of step n, to ts[0 .. S - 1]: the forward kernels' expressions (mi_ode_mlp.h k_fixed_mlp:
+// te + dt / 3.0f, te + dt * 2.0f / 3.0f, te + dt; fixed_grid.py:16-32: t + dt / 2, t + dt).  Zeros for the time-independent network, whose
+// first layer then adds 0 w_t = 0 whatever the grid holds.
+template <class DA>
+__device__ __forceinline__ void disc_stage_times(const DA& D, int n, float* ts) {
+  const float t0 = D.t0[n], hn = D.h[n];
+#pragma unroll
+  for (int q = 0; q < kDiscMaxStages; ++q) ts[q] = (!D.a.td || q >= D.S) ? 0.f : q == 0 ? t0 : t0 + (hn * D.tn[q]) / D.tdn[q];
+}
 
 template <int DP, int HP, int ACT>
 struct DiscCtx : AdjCtx<DP, HP, ACT> {
   using B = AdjCtx<DP, HP, ACT>;
   using G = AdjGeom<DP, HP>;
 
-  // f4 = f(xs) for the tile whose stage inputs are xs (4 elements per owner thread); X, H1, H2 go to the slot `act`.
-  // Every thread of the workgroup must call it.
-  __device__ __forceinline__ void fwd(const float* xs, float* f4, g_float* act) {
+  // f4 = f(t_s, xs) for the tile whose stage inputs are xs (4 elements per owner thread); X, H1, H2 go to the slot `act`.
+  // s: the stage - its time shifts the first layer's bias by t_s w_t, as in AdjCtx::eval (the product from DiscLds; 0 for the
+  // time-independent network).  Every thread of the workgroup must call it.
+  __device__ __forceinline__ void fwd(const float* xs, float* f4, g_float* act, int s) {
     constexpr int KS1 = G::KS1, KS2 = G::KS2;
+    using DL = DiscLds<DP, HP>;
     if (B::wave < G::NW3) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) B::s_x[(B::rbase + i) * G::LDX + B::col] = xs[i];
@@ -76,11 +106,12 @@ struct DiscCtx : AdjCtx<DP, HP, ACT> {
           c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[v], b, c1, 0, 0, 0);
         }
       }
+      const float b1e = B::b1v + B::s_w1[DL::OFF_TW + s * HP + B::col12];     // (read here: no register is held across the products)
       float h[8];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        h[i] = mlp_act<ACT>(c0[i] + B::b1v);
-        h[4 + i] = mlp_act<ACT>(c1[i] + B::b1v);
+        h[i] = mlp_act<ACT>(c0[i] + b1e);
+        h[4 + i] = mlp_act<ACT>(c1[i] + b1e);
         B::s_hA[(4 * B::lg + i) * G::LDH + B::col12] = h[i];
         B::s_hA[(16 + 4 * B::lg + i) * G::LDH + B::col12] = h[4 + i];
       }
@@ -212,7 +243,8 @@ struct DiscCtx : AdjCtx<DP, HP, ACT> {
 };
 
 // Step n of the reverse sweep for the workgroup's tiles k0 .. k0 + cnt - 1 (counted in ITS tiles): lambda_{n+1} -> lambda_n in D.lam, the
-// activations of every stage at scratch item blockIdx.x * chunk + (k - k0).
+// activations of every stage at scratch item blockIdx.x * chunk + (k - k0).  The bias shifts of the stages are those disc_prepare left
+// in DiscLds.
 template <int DP, int HP, int ACT>
 __device__ __attribute__((noinline)) void disc_tile_pass(const DiscArgs* D_, unsigned smem, int n, int k0, int cnt) {
   using G = AdjGeom<DP, HP>;
@@ -261,7 +293,7 @@ __device__ __attribute__((noinline)) void disc_tile_pass(const DiscArgs* D_, uns
           for (int j = 0; j < s; ++j) acc = j == 0 ? (hs * D.ha[s][0]) * ky[0][i] : acc + (hs * D.ha[s][j]) * ky[j][i];
           xs[i] = s == 0 ? y0e[i] : y0e[i] + acc;
         }
-        cx.fwd(xs, ky[s], act_tile + (long long)s * G::SLOT);
+        cx.fwd(xs, ky[s], act_tile + (long long)s * G::SLOT, s);
       }
     }
 #pragma unroll
@@ -293,6 +325,37 @@ __device__ __attribute__((noinline)) void disc_tile_pass(const DiscArgs* D_, uns
   }
 }
 
+// Before the passes of step n: the pass list of the weight-gradient pass (ntile tiles, every stage with coefficient 1 and its time) and
+// the bias shifts of the tile pass.  Every thread of the workgroup must call it; ends with a barrier.
+template <int DP, int HP>
+__device__ __attribute__((noinline)) void disc_prepare(const DiscArgs* D_, unsigned smem, unsigned ash_off, int n, int cnt, int accum) {
+  const MI_CONST DiscArgs& D = *(const MI_CONST DiscArgs*)uniform_p(D_);     // scalar loads
+  lds_AdjShared* const ash = (lds_AdjShared*)(size_t)__builtin_amdgcn_readfirstlane((int)ash_off);
+  lds_float* const s_tw = (lds_float*)(size_t)__builtin_amdgcn_readfirstlane((int)smem) + DiscLds<DP, HP>::OFF_TW;
+  n = __builtin_amdgcn_readfirstlane(n); cnt = __builtin_amdgcn_readfirstlane(cnt); accum = __builtin_amdgcn_readfirstlane(accum);
+  const int S = D.S, hd = D.a.p.s.rhs.hidden;
+  float ts[kDiscMaxStages];
+  disc_stage_times(D, n, ts);
+  if (threadIdx.x == 0) {
+    MI_LDS AdjWList& L = ash->wl[0];
+    L.n = S;
+#pragma unroll
+    for (int q = 0; q < kDiscMaxStages; ++q)
+      if (q < S) { L.slot[q] = q; L.c[0][q] = 1.f; L.c[1][q] = 0.f; L.ts[q] = ts[q]; }
+    L.ntile = cnt; L.cap = D.chunk; L.accum = accum;
+  }
+  if (D.a.td) {
+    const g_float* const wt = (const g_float*)D.a.p.s.rhs.w[0];            // row 0 of the time-dependent W1
+    for (int c = threadIdx.x; c < HP; c += blockDim.x) {
+      const float w = c < hd ? wt[c] : 0.f;
+#pragma unroll
+      for (int q = 0; q < kDiscMaxStages; ++q)
+        if (q < S) s_tw[q * HP + c] = ts[q] * w;
+    }
+  }
+  __syncthreads();
+}
+
 template <int DP, int HP, int ACT>
 __global__ __launch_bounds__((64 * AdjGeom<DP, HP>::NW)) void k_discrete_mlp(const DiscArgs* __restrict__ Dp) {
   using G = AdjGeom<DP, HP>;
@@ -312,6 +375,7 @@ __global__ __launch_bounds__((64 * AdjGeom<DP, HP>::NW)) void k_discrete_mlp(con
     cx.stage_weights(SA.rhs);
   }
   lds_float* const slice_scratch = (lds_float*)(size_t)smem + (DP * G::LW1 + HP * G::LW3);
+  for (int i = threadIdx.x; i < kDiscMaxStages * HP; i += blockDim.x) ((lds_float*)(size_t)smem)[DiscLds<DP, HP>::OFF_TW + i] = 0.f;
   if (threadIdx.x == 0) sh.ok = 1;
   __syncthreads();
   unsigned gen = 0;
@@ -326,13 +390,7 @@ __global__ __launch_bounds__((64 * AdjGeom<DP, HP>::NW)) void k_discrete_mlp(con
     for (int k0 = 0; k0 < my_tiles; k0 += D.chunk) {
       const int cnt = my_tiles - k0 < D.chunk ? my_tiles - k0 : D.chunk;
       for (int n = D.N - 2; n >= 0; --n) {
-        if (threadIdx.x == 0) {
-          AdjWList& L = ash_.wl[0];
-          L.n = D.S;
-          for (int q = 0; q < D.S; ++q) { L.slot[q] = q; L.c[0][q] = 1.f; L.c[1][q] = 0.f; L.ts[q] = 0.f; }
-          L.ntile = cnt; L.cap = D.chunk; L.accum = accum ? 1 : 0;
-        }
-        __syncthreads();
+        disc_prepare<DP, HP>(Dp, smem, ash_off, n, cnt, accum ? 1 : 0);
         const long long tk0 = (long long)wall_clock64();
         disc_tile_pass<DP, HP, ACT>(Dp, smem, n, k0, cnt);
         const long long tk1 = (long long)wall_clock64();

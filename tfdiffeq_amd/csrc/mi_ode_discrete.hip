@@ -13,6 +13,7 @@ struct mi_ode_discrete {
   mi_ode_discrete_desc d;
   int dp, hp;                  // padded widths of the kernel instantiation
   int S;                       // stages
+  int td;                      // 1: time-dependent first layer - theta starts with w_t [hidden]
   int P, Ppad, SL;
   int grid, block, chunk;
   size_t lds;
@@ -31,7 +32,7 @@ struct mi_ode_discrete {
 namespace {
 template <int DP, int HP>
 const void* disc_fn(int act, size_t* lds, int* block) {
-  *lds = AdjGeom<DP, HP>::lds_bytes();
+  *lds = DiscLds<DP, HP>::lds_bytes();
   *block = 64 * AdjGeom<DP, HP>::NW;
   switch (act) {
     case MLP_ACT_TANH: return (const void*)k_discrete_mlp<DP, HP, MLP_ACT_TANH>;
@@ -47,6 +48,15 @@ const void* disc_fn_dims(int dp, int hp, int act, size_t* lds, int* block) {
   return disc_fn<64, 128>(act, lds, block);
 }
 int pad16(int v, int lo, int hi) { return v <= lo ? lo : hi; }
+// alpha as the quotient the forward step functions divide by: 1/3 -> h 1 / 3, 2/3 -> h 2 / 3, 1/2 -> h 1 / 2, 1 -> h 1 / 1 (exact);
+// any other alpha: h alpha / 1 (documented in mi_ode.h: the tableaus of the four supported methods take the branches above)
+void stage_quotient(double alpha, float* num, float* den) {
+  for (int dn = 1; dn <= 3; ++dn) {
+    const double v = alpha * dn;
+    if (fabs(v - nearbyint(v)) < 1e-12) { *num = (float)nearbyint(v); *den = (float)dn; return; }
+  }
+  *num = (float)alpha; *den = 1.f;
+}
 }  // namespace
 
 extern "C" int mi_ode_discrete_destroy(mi_ode_discrete_handle h) {
@@ -64,8 +74,13 @@ extern "C" int mi_ode_discrete_destroy(mi_ode_discrete_handle h) {
 extern "C" int64_t mi_ode_discrete_num_params(mi_ode_discrete_handle h) { return h ? (int64_t)h->P : -1; }
 
 extern "C" int mi_ode_discrete_create(const mi_ode_discrete_desc* desc, mi_ode_discrete_handle* out) {
+  return mi_ode_discrete_create_td(desc, 0, out);
+}
+
+extern "C" int mi_ode_discrete_create_td(const mi_ode_discrete_desc* desc, int32_t time_dependent, mi_ode_discrete_handle* out) {
   if (desc == nullptr || out == nullptr) { mi_set_error("null argument"); return MI_ODE_E_INVALID; }
   *out = nullptr;
+  if (time_dependent != 0 && time_dependent != 1) { mi_set_error("fused discrete sweep: time_dependent must be 0 or 1"); return MI_ODE_E_INVALID; }
   const mi_ode_tableau& tb = desc->tableau;
   if (desc->batch < 1 || desc->dim < 1 || desc->dim > 64 || desc->hidden < 1 || desc->hidden > 128) {
     mi_set_error("fused discrete sweep: batch >= 1, 1 <= dim <= 64, 1 <= hidden <= 128"); return MI_ODE_E_INVALID;
@@ -83,11 +98,12 @@ extern "C" int mi_ode_discrete_create(const mi_ode_discrete_desc* desc, mi_ode_d
   memset(h, 0, sizeof(*h));
   h->d = *desc;
   h->S = tb.n_stages + 1;
+  h->td = time_dependent;
   h->dp = pad16(desc->dim, 16, 64);
   h->hp = pad16(desc->hidden, 16, 128);
   for (int act = 0; act < 3; ++act) h->fn[act] = disc_fn_dims(h->dp, h->hp, act, &h->lds, &h->block);
   const int d = desc->dim, hd = desc->hidden;
-  h->P = d * hd + hd + hd * hd + hd + hd * d + d;
+  h->P = h->td * hd + d * hd + hd + hd * hd + hd + hd * d + d;
   h->Ppad = (h->P + 63) / 64 * 64;
   h->ntiles = (desc->batch + 31) / 32;
   int dev = 0, cus = 0, per_cu = 0;
@@ -155,7 +171,11 @@ extern "C" int mi_ode_discrete_sweep(mi_ode_discrete_handle h, const mi_ode_rhs*
       rhs->w[2] == nullptr) {
     mi_set_error("fused discrete sweep: rhs must be the MLP descriptor the handle was created for"); return MI_ODE_E_INVALID;
   }
-  if (rhs->scalars[1] != 0.0) { mi_set_error("fused discrete sweep: the time-independent network only"); return MI_ODE_E_INVALID; }
+  if ((rhs->scalars[1] != 0.0) != (h->td != 0)) {
+    mi_set_error("fused discrete sweep: the handle was created for a time-%s network, rhs->scalars[1] says time-%s",
+                 h->td ? "dependent" : "independent", h->td ? "independent" : "dependent");
+    return MI_ODE_E_INVALID;
+  }
   const int act = (int)rhs->scalars[0];
   if (act < 0 || act > 2) { mi_set_error("fused discrete sweep: unknown activation code %d", act); return MI_ODE_E_INVALID; }
   hipStream_t st = (hipStream_t)stream;
@@ -178,14 +198,19 @@ extern "C" int mi_ode_discrete_sweep(mi_ode_discrete_handle h, const mi_ode_rhs*
   A.p.spin_first = h->spin_first < h->spin_limit ? h->spin_first : h->spin_limit;
   A.p.sleep_first = h->grid <= 32 ? 16 : 32; A.p.sleep_poll = 2;
   A.act = h->act; A.wpart = h->wpart;
-  A.P = h->P; A.Ppad = h->Ppad; A.SL = h->SL;
+  A.P = h->P; A.Ppad = h->Ppad; A.SL = h->SL; A.td = h->td;
   D.ys = (const float*)ys_dev; D.gys = (const float*)grad_ys_dev; D.lam = (float*)grad_y0_out_dev; D.th_out = (float*)grad_theta_out_dev;
   D.res = h->res;
   D.N = h->d.n_points; D.S = h->S; D.chunk = h->chunk;
   for (int i = 1; i < h->S; ++i)
     for (int j = 0; j < i; ++j) D.ha[i][j] = (float)tb.beta[i - 1][j];
   for (int i = 0; i < h->S; ++i) D.hb[i] = (float)tb.c_sol[i];
-  for (int n = 0; n + 1 < D.N; ++n) D.h[n] = (float)t_host[n + 1] - (float)t_host[n];     // solvers.py:84: the grid in the state dtype
+  D.tn[0] = 0.f; D.tdn[0] = 1.f;
+  for (int i = 1; i < h->S; ++i) stage_quotient(tb.alpha[i - 1], &D.tn[i], &D.tdn[i]);
+  for (int n = 0; n + 1 < D.N; ++n) {                      // solvers.py:84: the grid in the state dtype
+    D.t0[n] = (float)t_host[n];
+    D.h[n] = (float)t_host[n + 1] - (float)t_host[n];
+  }
   MI_HIP(hipMemcpyAsync(h->args_dev, h->args_host, sizeof(DiscArgs), hipMemcpyHostToDevice, st));
   const DiscArgs* dev_args = h->args_dev;
   void* args[] = {(void*)&dev_args};

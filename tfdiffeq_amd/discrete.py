@@ -20,8 +20,9 @@ Four engines:
   * fused row-local sweep - opt-in (`lower='auto'` / True, module default LOWER): a plain Python callable the tracer lowers to a row-local
     program (lower.py, state of up to 32 elements per trajectory) gets the vjp of its trace as generated device code, and the whole
     backward, all steps, is ONE launch with a trajectory per lane (csrc/mi_ode_discrete_row.h), float32 and float64;
-  * fused mlp sweep - models.ODEFunc / rhs.MLP (relu, softplus, tanh), float32, time independent, dim <= 64, hidden <= 128, all six
-    parameters trainable: the whole backward, all steps, is ONE launch (csrc/mi_ode_discrete.h);
+  * fused mlp sweep - models.ODEFunc / rhs.MLP (relu, softplus, tanh), float32, time dependent or not, dim <= 64, hidden <= 128, any
+    subset of the six parameters trainable, up to 1024 steps per segment: the whole backward, all steps, is ONE launch
+    (csrc/mi_ode_discrete.h); a float64 network stays on the generic sweep;
   * generic sweep   - any `func`, any dtype, tuple states: per step one taped re-evaluation in torch ops and one torch.autograd.grad call.
 
 Scope: euler, midpoint, heun / huen and rk4 (the 3/8 rule) with eps == 0, on the default grid (`t` itself) and - opt-in, `own_grid=True` /
@@ -160,9 +161,9 @@ def generic_sweep(func, params, ys, t, grad_ys, method):
 
 class _FusedDiscreteEngine(object):
     """Owns one mi_ode_discrete handle: the reverse sweep of `n_points - 1` steps of `method` for a [batch, dim] float32 state and the
-    dim -> hidden -> hidden -> dim MLP, one launch."""
+    dim -> hidden -> hidden -> dim MLP (time_dependent: (1 + dim) -> hidden, the first layer sees concat([t, x])), one launch."""
 
-    def __init__(self, batch, dim, hidden, method, n_points, device, chunk_tiles=0):
+    def __init__(self, batch, dim, hidden, method, n_points, device, chunk_tiles=0, time_dependent=False):
         from .solvers import _fill_tableau
         self.lib = N.load()
         self.device = torch.device(device)
@@ -173,9 +174,9 @@ class _FusedDiscreteEngine(object):
         self.desc = d
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            N.check(self.lib.mi_ode_discrete_create(C.byref(d), C.byref(h)), 'mi_ode_discrete_create')
+            N.check(self.lib.mi_ode_discrete_create_td(C.byref(d), 1 if time_dependent else 0, C.byref(h)), 'mi_ode_discrete_create_td')
         self.h = h
-        self.batch, self.dim, self.n_points = int(batch), int(dim), int(n_points)
+        self.batch, self.dim, self.n_points, self.time_dependent = int(batch), int(dim), int(n_points), bool(time_dependent)
         self.n_params = int(self.lib.mi_ode_discrete_num_params(h))
         self.stats = N.Stats()
 
@@ -210,10 +211,12 @@ class _FusedDiscreteEngine(object):
         return g_y0, g_th
 
 
-def _cached_engine(*key):
+def _cached_engine(batch, dim, hidden, method, n_points, device, chunk_tiles=0, time_dependent=False):
+    key = (batch, dim, hidden, method, n_points, device, bool(time_dependent), chunk_tiles)
     eng = _ENGINES.get(key)
     if eng is None:
-        eng = _FusedDiscreteEngine(*key)                 # (evict only after a successful create: a refusal must not cost live engines)
+        # (evict only after a successful create: a refusal must not cost live engines)
+        eng = _FusedDiscreteEngine(batch, dim, hidden, method, n_points, device, chunk_tiles, time_dependent)
         while len(_ENGINES) >= 4:
             _ENGINES.pop(next(iter(_ENGINES))).close()
         _ENGINES[key] = eng
@@ -248,14 +251,17 @@ def _fused_plan(func, params, method, tensor_input, like):
     mlp = get()
     if mlp is None or getattr(mlp, 'kind', None) != N.RHS_MLP_TANH:
         return None, 'the activation has no fused MLP kernel (relu, softplus, tanh do)'
-    if mlp.time_dependent:
-        return None, 'a time-dependent network (the stage time enters the first layer)'
     y1 = like[0]
     if y1.dim() < 2 or not mlp.supports(y1):
         return None, 'outside the tile box of rhs.MLP.supports (dim <= %d, hidden <= %d, state [batch, dim])' % (mlp.MAX_DIM, mlp.MAX_HIDDEN)
     want = [p for l in layers for p in (l.weight, l.bias)]
-    if len(params) != 6 or any(a is not b for a, b in zip(params, want)):
-        return None, 'frozen or extra parameters (the kernel produces the gradients of all six tensors of the network)'
+    # any duplicate-free subset of the six, by identity: the kernel computes all six gradients, the call returns those it asked for
+    if any(a is b for i, a in enumerate(want) for b in want[:i]):
+        return None, 'tied parameters (two of the six slots of the network hold the same tensor: its gradient is the sum of two of the kernel\'s)'
+    if any(a is b for i, a in enumerate(params) for b in params[:i]):
+        return None, 'a tensor listed twice among the parameters'
+    if any(not any(p is w_ for w_ in want) for p in params):
+        return None, 'frozen or extra parameters (the kernel produces the gradients of the six tensors of the network, or of a subset of them)'
     if any(p.dtype != torch.float32 or p.device != like.device for p in want):
         return None, 'parameters in another dtype or on another device than the state'
     n_points = int(like.shape[0])
@@ -263,7 +269,8 @@ def _fused_plan(func, params, method, tensor_input, like):
         return None, 'more than 1024 steps'
     batch = y1.numel() // y1.shape[-1]
     try:
-        eng = _cached_engine(batch, int(y1.shape[-1]), int(mlp.hidden), 'heun' if method == 'huen' else method, n_points, str(like.device), int(CHUNK_TILES))
+        eng = _cached_engine(batch, int(y1.shape[-1]), int(mlp.hidden), 'heun' if method == 'huen' else method, n_points, str(like.device), int(CHUNK_TILES),
+                             bool(mlp.time_dependent))
     except N.NativeError as e:                           # e.g. no memory for the activation scratch
         return None, 'the fused engine could not be created (%s)' % e
     return (eng, mlp), ''
@@ -739,7 +746,9 @@ def _stored_sweep(ctx, t, ans, grad_output):
                 g_y0, theta = eng.sweep(mlp, t.to(like.dtype).double().cpu().numpy(), like.reshape(shape[0], -1, shape[-1]),
                                         grad_output[0].reshape(shape[0], -1, shape[-1]))
                 flat = canonical_to_module_order(func, theta)
-                gp = [g.reshape(p.shape).to(p.dtype) for g, p in zip(torch.split(flat, [p.numel() for p in params]), params)]
+                six = [p for l in (func.fc1, func.fc2, func.fc3) for p in (l.weight, l.bias)]
+                of = {id(p): g for p, g in zip(six, torch.split(flat, [p.numel() for p in six]))}
+                gp = [of[id(p)].reshape(p.shape).to(p.dtype) for p in params]        # (a frozen tensor is not among params)
             stats = {'engine': 'fused mlp sweep', 'n_steps': n_steps, 'n_launches': int(eng.stats.n_launches),
                      'why': '', 'method': method, 'forward': ctx.forward_stats}
             return (g_y0.reshape(shape[1:]),), gp, stats
