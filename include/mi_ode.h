@@ -437,6 +437,24 @@ int64_t mi_ode_discrete_num_params(mi_ode_discrete_handle h);
 int mi_ode_discrete_sweep(mi_ode_discrete_handle h, const mi_ode_rhs* rhs, const double* t_host, const void* ys_dev,
                           const void* grad_ys_dev, void* grad_y0_out_dev, void* grad_theta_out_dev, mi_ode_stats* stats, void* stream);
 
+/* ---- (A''''-64) the same reverse sweep for the ODEFunc MLP in fp64, ONE launch ---------------------------------------------------- */
+/* The float64 twin of section A'''' (csrc/mi_ode_discrete64.h): same recursion, same schedule, same determinism, the operand plan of the
+ * float64 forward kernels - weights streamed from packed copies, in both orientations, refreshed in front of every sweep.  The descriptor
+ * is mi_ode_discrete_desc (same box: dim <= 64, hidden <= 128, at most 4 stages, 2 <= n_points <= 1025; chunk_tiles as there, a scratch
+ * slot is 32 (2 DP + 4 HP) doubles); time_dependent as in mi_ode_discrete_create_td, the stage times are formed in double.
+ * mi_ode_discrete64_sweep: every device buffer is fp64, grad_theta_out_dev in the canonical order of (A') - w_t first when time
+ * dependent.  MI_ODE_E_INVALID when rhs->scalars[1] disagrees with the handle's flag or the activation code is unknown.  Deterministic:
+ * two calls give identical bits.  Blocks until done; returns status bits (>= 0) or an error (< 0).  stats->n_launches == 1: it counts the
+ * sweep kernel, as the float64 forward family counts its kernels - the two small pack launches enqueued in front of it are not counted. */
+typedef struct mi_ode_discrete64* mi_ode_discrete64_handle;
+int mi_ode_discrete64_create(const mi_ode_discrete_desc* desc, int32_t time_dependent, mi_ode_discrete64_handle* out);
+int mi_ode_discrete64_destroy(mi_ode_discrete64_handle h);
+int64_t mi_ode_discrete64_num_params(mi_ode_discrete64_handle h);
+int mi_ode_discrete64_sweep(mi_ode_discrete64_handle h, const mi_ode_rhs* rhs, const double* t_host, const void* ys_dev,
+                            const void* grad_ys_dev, void* grad_y0_out_dev, void* grad_theta_out_dev, mi_ode_stats* stats, void* stream);
+/* where the time of the last sweep went, microseconds of workgroup 0: {tile passes, weight-gradient passes, final hand-off + fold} */
+int mi_ode_discrete64_profile(mi_ode_discrete64_handle h, double* out3);
+
 /* ---- (A''''') the same reverse sweep for a row-local f with a generated vjp (tfdiffeq_amd/lower.py), ONE launch ------------------------ */
 /* rhs: MI_ODE_RHS_PLUGIN with `plugin` = what a discrete plugin's mi_ode_discrete_plugin_get(dtype) returned (csrc/mi_ode_discrete_plugin.h);
  * scalars and w[0] as for the row-local plugin of the same callable.  A trajectory per lane; the parameter gradient is reduced in a fixed

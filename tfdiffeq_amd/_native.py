@@ -227,6 +227,12 @@ _PROTOS = {
     'mi_ode_discrete_num_params': (C.c_int64, [C.c_void_p]),
     'mi_ode_discrete_sweep': (C.c_int, [C.c_void_p, C.POINTER(Rhs), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_discrete64_create': (C.c_int, [C.POINTER(DiscreteDesc), C.c_int32, C.POINTER(C.c_void_p)]),
+    'mi_ode_discrete64_destroy': (C.c_int, [C.c_void_p]),
+    'mi_ode_discrete64_num_params': (C.c_int64, [C.c_void_p]),
+    'mi_ode_discrete64_sweep': (C.c_int, [C.c_void_p, C.POINTER(Rhs), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_discrete64_profile': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'mi_ode_discrete_row_sweep': (C.c_int, [C.POINTER(DiscreteRowDesc), C.POINTER(Rhs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(Stats), C.c_void_p]),
     'mi_ode_discrete_linear_create': (C.c_int, [C.POINTER(DiscreteLinearDesc), C.POINTER(C.c_void_p)]),

@@ -13,7 +13,7 @@ lambda_{n+1} = dL/dy_{n+1}, for i = s .. 1:
 and lambda_n = lambda_{n+1} + sum_i Ybar_i + gbar_n (gbar_n: the output gradient at grid point n).  The forward solution on the default
 grid holds every y_n, so the checkpoints are free and each step is recomputed from its own.
 
-Four engines:
+Five engines:
   * fused linear sweep - opt-in (`linear='auto'` / True, module default LINEAR): f(t, y) = y W (+ b) - models.LinearODEFunc, or a callable the
     tracer puts in the 'linear' family (`y @ W`, `y @ W + b`, torch.nn.Linear(d, d)) - float32 and float64, dim <= 128: the whole backward,
     all steps, is ONE launch on the matrix cores (csrc/mi_ode_discrete_linear.h);
@@ -22,7 +22,10 @@ Four engines:
     backward, all steps, is ONE launch with a trajectory per lane (csrc/mi_ode_discrete_row.h), float32 and float64;
   * fused mlp sweep - models.ODEFunc / rhs.MLP (relu, softplus, tanh), float32, time dependent or not, dim <= 64, hidden <= 128, any
     subset of the six parameters trainable, up to 1024 steps per segment: the whole backward, all steps, is ONE launch
-    (csrc/mi_ode_discrete.h); a float64 network stays on the generic sweep;
+    (csrc/mi_ode_discrete.h); a float64 network stays on the generic sweep unless the next engine is switched on;
+  * fused mlp sweep (float64) - opt-in (`mlp64='auto'` / True, module default MLP64): the same network, box and step limit in float64, all
+    six parameters in float64: the whole backward, all steps, is ONE launch on the f64 matrix cores, weights streamed from packed copies
+    in both orientations (csrc/mi_ode_discrete64.h);
   * generic sweep   - any `func`, any dtype, tuple states: per step one taped re-evaluation in torch ops and one torch.autograd.grad call.
 
 Scope: euler, midpoint, heun / huen and rk4 (the 3/8 rule) with eps == 0, on the default grid (`t` itself) and - opt-in, `own_grid=True` /
@@ -61,8 +64,11 @@ OWN_GRID = False              # default of odeint_discrete(own_grid=...): False 
 GRID_BYTES = 1 << 30          # own grid: bound on the recomputed grid states plus their gradients; beyond it the grid is swept in segments
 GRID_KERNEL = True            # own grid, linear system: the one-launch kernel that recomputes its checkpoints (csrc/mi_ode_discrete_linear.h,
                               # GRID = true); False: the recompute on the grid and the default-grid linear sweep
+MLP64 = False                 # default of odeint_discrete(mlp64=...): False - a float64 network takes the generic sweep, as before; 'auto' - the fused
+                              # float64 mlp sweep where it applies; True - raise ValueError where it does not
 ROW_GRID = 0                  # workgroups of the fused row-local sweep; 0: one per 256 trajectories, up to 1024
 _ENGINES = {}
+_ENGINES64 = {}
 _LINEAR_ENGINES = {}
 
 
@@ -160,8 +166,10 @@ def generic_sweep(func, params, ys, t, grad_ys, method):
 
 
 class _FusedDiscreteEngine(object):
-    """Owns one mi_ode_discrete handle: the reverse sweep of `n_points - 1` steps of `method` for a [batch, dim] float32 state and the
+    """Owns one mi_ode_discrete handle: the reverse sweep of `n_points - 1` steps of `method` for a [batch, dim] state in `dtype` and the
     dim -> hidden -> hidden -> dim MLP (time_dependent: (1 + dim) -> hidden, the first layer sees concat([t, x])), one launch."""
+    dtype = torch.float32
+    _create, _destroy, _num_params, _sweep = 'mi_ode_discrete_create_td', 'mi_ode_discrete_destroy', 'mi_ode_discrete_num_params', 'mi_ode_discrete_sweep'
 
     def __init__(self, batch, dim, hidden, method, n_points, device, chunk_tiles=0, time_dependent=False):
         from .solvers import _fill_tableau
@@ -174,15 +182,15 @@ class _FusedDiscreteEngine(object):
         self.desc = d
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            N.check(self.lib.mi_ode_discrete_create_td(C.byref(d), 1 if time_dependent else 0, C.byref(h)), 'mi_ode_discrete_create_td')
+            N.check(getattr(self.lib, self._create)(C.byref(d), 1 if time_dependent else 0, C.byref(h)), self._create)
         self.h = h
         self.batch, self.dim, self.n_points, self.time_dependent = int(batch), int(dim), int(n_points), bool(time_dependent)
-        self.n_params = int(self.lib.mi_ode_discrete_num_params(h))
+        self.n_params = int(getattr(self.lib, self._num_params)(h))
         self.stats = N.Stats()
 
     def close(self):
         if getattr(self, 'h', None):
-            self.lib.mi_ode_discrete_destroy(self.h)
+            getattr(self.lib, self._destroy)(self.h)
             self.h = None
 
     def __del__(self):
@@ -194,14 +202,14 @@ class _FusedDiscreteEngine(object):
     def sweep(self, mlp, t, ys, grad_ys):
         """(grad_y0 [batch, dim], grad_theta [P] in canonical order) from the forward solution and its gradient, both [N, batch, dim]."""
         r = N.Rhs()
-        keep = mlp.fill(r, torch.float32, self.device)
+        keep = mlp.fill(r, self.dtype, self.device)
         ys, grad_ys = ys.contiguous(), grad_ys.contiguous()
-        g_y0 = torch.empty(self.batch, self.dim, dtype=torch.float32, device=self.device)
-        g_th = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
+        g_y0 = torch.empty(self.batch, self.dim, dtype=self.dtype, device=self.device)
+        g_th = torch.empty(self.n_params, dtype=self.dtype, device=self.device)
         tt = (C.c_double * self.n_points)(*[float(v) for v in t])
         with torch.cuda.device(self.device):
-            rc = N.check(self.lib.mi_ode_discrete_sweep(self.h, C.byref(r), tt, ys.data_ptr(), grad_ys.data_ptr(), g_y0.data_ptr(), g_th.data_ptr(),
-                                                        C.byref(self.stats), N.stream_ptr(self.device)), 'mi_ode_discrete_sweep')
+            rc = N.check(getattr(self.lib, self._sweep)(self.h, C.byref(r), tt, ys.data_ptr(), grad_ys.data_ptr(), g_y0.data_ptr(), g_th.data_ptr(),
+                                                        C.byref(self.stats), N.stream_ptr(self.device)), self._sweep)
         del keep
         if rc != 0:
             from .adjoint import HandoffTimeout
@@ -223,24 +231,54 @@ def _cached_engine(batch, dim, hidden, method, n_points, device, chunk_tiles=0, 
     return eng
 
 
+class _FusedDiscreteEngine64(_FusedDiscreteEngine):
+    """Owns one mi_ode_discrete64 handle: _FusedDiscreteEngine for a float64 state and float64 parameters (csrc/mi_ode_discrete64.h)."""
+    dtype = torch.float64
+    _create, _destroy, _num_params, _sweep = ('mi_ode_discrete64_create', 'mi_ode_discrete64_destroy', 'mi_ode_discrete64_num_params',
+                                              'mi_ode_discrete64_sweep')
+
+    def profile(self):
+        """Where the time of the last sweep went, microseconds of workgroup 0: (tile passes, weight-gradient passes, hand-off + fold)."""
+        out = (C.c_double * 3)()
+        N.check(self.lib.mi_ode_discrete64_profile(self.h, out), 'mi_ode_discrete64_profile')
+        return tuple(float(v) for v in out)
+
+
+def _cached_engine64(batch, dim, hidden, method, n_points, device, chunk_tiles=0, time_dependent=False):
+    """_cached_engine for the float64 kernel: the same size-4 eviction, the dtype in the key (shape first, the chunk last)."""
+    key = (batch, dim, hidden, method, n_points, device, 'float64', bool(time_dependent), chunk_tiles)
+    eng = _ENGINES64.get(key)
+    if eng is None:
+        eng = _FusedDiscreteEngine64(batch, dim, hidden, method, n_points, device, chunk_tiles, time_dependent)
+        while len(_ENGINES64) >= 4:
+            _ENGINES64.pop(next(iter(_ENGINES64))).close()
+        _ENGINES64[key] = eng
+    return eng
+
+
 def clear_engines():
-    """Empties both engine caches.  The MLP engines are closed here.  A linear engine is only dropped: a call that has run forward and not
+    """Empties the engine caches.  The MLP engines (float32 and float64) are closed here.  A linear engine is only dropped: a call that has run forward and not
     yet backward still holds it, so its device memory is released when the last such graph is gone, which need not be now."""
     while _ENGINES:
         _ENGINES.pop(next(iter(_ENGINES))).close()
+    while _ENGINES64:
+        _ENGINES64.pop(next(iter(_ENGINES64))).close()
     _LINEAR_ENGINES.clear()                              # (dropped, not closed: see _cached_linear_engine)
 
 
-def _fused_plan(func, params, method, tensor_input, like):
-    """((engine, descriptor), '') when the fused kernel takes this backward, else (None, why not) - in the style of odeint.plan."""
+def _fused_plan(func, params, method, tensor_input, like, mlp64=False):
+    """((engine, descriptor), '') when the fused kernel takes this backward, else (None, why not) - in the style of odeint.plan.
+    mlp64: anything but False lets a float64 state take the float64 kernel (the engine then has dtype torch.float64)."""
     if not FUSED:
         return None, 'discrete.FUSED is False'
     if not tensor_input:
         return None, 'a tuple state'
     if not like.is_cuda:
         return None, 'a host tensor'
-    if like.dtype != torch.float32:
+    if like.dtype != torch.float32 and (mlp64 is False or mlp64 is None):
         return None, 'dtype %s (the fused sweep is float32)' % str(like.dtype).replace('torch.', '')
+    if like.dtype not in (torch.float32, torch.float64):
+        return None, 'dtype %s (the fused sweeps are float32 and float64)' % str(like.dtype).replace('torch.', '')
     get = getattr(func, 'device_rhs', None)
     try:
         layers = (func.fc1, func.fc2, func.fc3)
@@ -262,15 +300,16 @@ def _fused_plan(func, params, method, tensor_input, like):
         return None, 'a tensor listed twice among the parameters'
     if any(not any(p is w_ for w_ in want) for p in params):
         return None, 'frozen or extra parameters (the kernel produces the gradients of the six tensors of the network, or of a subset of them)'
-    if any(p.dtype != torch.float32 or p.device != like.device for p in want):
+    if any(p.dtype != like.dtype or p.device != like.device for p in want):
         return None, 'parameters in another dtype or on another device than the state'
     n_points = int(like.shape[0])
     if n_points - 1 > 1024:
         return None, 'more than 1024 steps'
     batch = y1.numel() // y1.shape[-1]
     try:
-        eng = _cached_engine(batch, int(y1.shape[-1]), int(mlp.hidden), 'heun' if method == 'huen' else method, n_points, str(like.device), int(CHUNK_TILES),
-                             bool(mlp.time_dependent))
+        cached = _cached_engine64 if like.dtype == torch.float64 else _cached_engine
+        eng = cached(batch, int(y1.shape[-1]), int(mlp.hidden), 'heun' if method == 'huen' else method, n_points, str(like.device), int(CHUNK_TILES),
+                     bool(mlp.time_dependent))
     except N.NativeError as e:                           # e.g. no memory for the activation scratch
         return None, 'the fused engine could not be created (%s)' % e
     return (eng, mlp), ''
@@ -704,7 +743,8 @@ def _params_of(func, y0, t):
 
 def _stored_sweep(ctx, t, ans, grad_output):
     """The reverse sweep over a stored trajectory - `ans`: the states at the grid points `t`, `grad_output`: the gradient of the loss with
-    respect to each - on the first engine that takes it: fused linear, fused row-local, fused mlp, generic.  Returns (tuple of gradients
+    respect to each - on the first engine that takes it: fused linear, fused row-local, fused mlp (float32, or float64 behind
+    ctx.mlp64), generic.  Returns (tuple of gradients
     at y0, list of parameter gradients, the last_backward_stats of the sweep)."""
     func, method, params = ctx.func, ctx.method, ctx.params
     like = ans[0]
@@ -732,7 +772,7 @@ def _stored_sweep(ctx, t, ans, grad_output):
         stats = {'engine': 'fused row-local sweep', 'n_steps': n_steps, 'n_launches': n_launches, 'why': '',
                  'method': method, 'n_params': row.n_params, 'forward': ctx.forward_stats}
         return (g_y0.reshape(shape[1:]),), gp, stats
-    plan, why = _fused_plan(func, params, method, ctx.tensor_input, like)
+    plan, why = _fused_plan(func, params, method, ctx.tensor_input, like, getattr(ctx, 'mlp64', False))
     if row_why:
         why = 'fused row-local sweep: %s; fused mlp sweep: %s' % (row_why, why)
     if lin_why:
@@ -749,7 +789,8 @@ def _stored_sweep(ctx, t, ans, grad_output):
                 six = [p for l in (func.fc1, func.fc2, func.fc3) for p in (l.weight, l.bias)]
                 of = {id(p): g for p, g in zip(six, torch.split(flat, [p.numel() for p in six]))}
                 gp = [of[id(p)].reshape(p.shape).to(p.dtype) for p in params]        # (a frozen tensor is not among params)
-            stats = {'engine': 'fused mlp sweep', 'n_steps': n_steps, 'n_launches': int(eng.stats.n_launches),
+            name = 'fused mlp sweep (float64)' if getattr(eng, 'dtype', None) is torch.float64 else 'fused mlp sweep'
+            stats = {'engine': name, 'n_steps': n_steps, 'n_launches': int(eng.stats.n_launches),
                      'why': '', 'method': method, 'forward': ctx.forward_stats}
             return (g_y0.reshape(shape[1:]),), gp, stats
         except HandoffTimeout as e:                  # the GPU is shared with another persistent kernel: nothing was committed
@@ -918,7 +959,35 @@ class _OdeintDiscreteLinearGrid(torch.autograd.Function):
         return (None, None, None, None) + _OdeintDiscrete.backward(ctx, *grad_output)
 
 
-def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=None, own_grid=None, _forward_func=None):
+class _OdeintDiscreteMlp64(torch.autograd.Function):
+    """_OdeintDiscreteLinearGrid (each plan None where its route is off) with the call's `mlp64` in front of its arguments."""
+
+    @staticmethod
+    def forward(ctx, mlp64, grid_plan, linear_grid_plan, linear_plan, row_plan, *args):
+        ctx.mlp64 = mlp64
+        ctx.grid_plan, ctx.linear_grid_plan, ctx.linear_plan, ctx.row_plan = grid_plan, linear_grid_plan, linear_plan, row_plan
+        return _OdeintDiscrete.forward(ctx, *args)
+
+    @staticmethod
+    def backward(ctx, *grad_output):
+        return (None, None, None, None, None) + _OdeintDiscrete.backward(ctx, *grad_output)
+
+
+def _mlp64_check(mlp64, func, params, method, tensor_input, ys, n_points):
+    """odeint_discrete(mlp64=True): ValueError, at the call, where the float64 kernel will not take the backward (planned for a stored
+    trajectory of n_points states like ys[0])."""
+    if mlp64 is not True or not torch.is_grad_enabled():
+        return
+    y = ys[0].detach()
+    if tensor_input and y.dtype != torch.float64:
+        raise ValueError('odeint_discrete(mlp64=True): the fused float64 mlp sweep does not take this call: dtype %s'
+                         % str(y.dtype).replace('torch.', ''))
+    plan, why = _fused_plan(func, params, method, tensor_input, y.unsqueeze(0).expand((int(n_points),) + tuple(y.shape)), True)
+    if plan is None:
+        raise ValueError('odeint_discrete(mlp64=True): the fused float64 mlp sweep does not take this call: ' + why)
+
+
+def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=None, own_grid=None, mlp64=None, _forward_func=None):
     """`odeint(func, y0, t, method=method, options=options)` - same values, same engine - whose result is differentiable with respect to
     y0 and func's trainable tensors, with the gradient of the DISCRETE map the solver computed (what back-propagating through the
     reference's solver gives), not the continuous adjoint's.
@@ -942,8 +1011,13 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=
     callable the tracer puts in the 'linear' family: `y @ W`, `y @ W + b`, torch.nn.Linear(d, d)), float32 / float64, dim <= 128, runs its
     whole backward in one launch on the matrix cores (csrc/mi_ode_discrete_linear.h), anything else falls to the routes above with the
     reason in last_backward_stats['why']; True - ValueError with that reason, here at the call.
+    mlp64: None - the module default `discrete.MLP64` (False); False - a float64 models.ODEFunc takes the generic sweep, as before; 'auto' - it
+    runs its whole backward in one launch on the f64 matrix cores (csrc/mi_ode_discrete64.h: same box, parameter rules and step limit as the
+    float32 fused mlp sweep, state and all six parameters float64; with own_grid=True through the same recompute, segments included),
+    anything else falls to the generic sweep with the reason in last_backward_stats['why']; True - ValueError with that reason, here at
+    the call.  The linear and row-local sweeps keep their precedence, and a float32 network is not affected.
     `odeint_discrete.last_backward_stats`: {'engine': 'fused linear sweep' | 'fused linear sweep (own grid)' | 'fused row-local sweep' |
-    'fused mlp sweep' | 'generic sweep', 'n_steps',
+    'fused mlp sweep' | 'fused mlp sweep (float64)' | 'generic sweep', 'n_steps',
     'n_launches', 'why'} of the last backward ('why': the reason the fused kernels were not used)."""
     own_grid = OWN_GRID if own_grid is None else own_grid
     if own_grid not in (False, True):
@@ -955,6 +1029,9 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=
     linear = LINEAR if linear is None else linear
     if linear not in (False, True, 'auto'):
         raise ValueError("odeint_discrete: linear must be False, True or 'auto', not %r" % (linear,))
+    mlp64 = MLP64 if mlp64 is None else mlp64
+    if mlp64 not in (False, True, 'auto'):
+        raise ValueError("odeint_discrete: mlp64 must be False, True or 'auto', not %r" % (mlp64,))
     tensor_input = isinstance(y0, torch.Tensor)
     ys = (y0,) if tensor_input else tuple(y0)
     for y_ in ys:
@@ -984,7 +1061,13 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=
             row_plan = _row_plan(func, params, method, y0) if torch.is_grad_enabled() else (None, 'gradients are disabled')
             if lower is True and row_plan[0] is None:
                 raise ValueError('odeint_discrete(lower=True): the fused row-local sweep does not take this call: ' + row_plan[1])
-        out = _OdeintDiscreteLinearGrid.apply(gplan, kern_plan, lin_plan, row_plan, func, fwd, method, options, t, tensor_input, len(params), *params, *ys)
+        rest = (func, fwd, method, options, t, tensor_input, len(params)) + tuple(params) + tuple(ys)
+        if mlp64 is not False:
+            if kern_plan[0] is None and lin_plan[0] is None and (row_plan is None or row_plan[0] is None):
+                _mlp64_check(mlp64, func, params, method, tensor_input, ys, seg[1] - seg[0] + 1)
+            out = _OdeintDiscreteMlp64.apply(mlp64, gplan, kern_plan, lin_plan, row_plan, *rest)
+        else:
+            out = _OdeintDiscreteLinearGrid.apply(gplan, kern_plan, lin_plan, row_plan, *rest)
         return out[0] if tensor_input else tuple(out)
     if linear is not False:
         lin_plan = _linear_plan(func, params, method, y0, n_points=t.numel()) if torch.is_grad_enabled() else (None, 'gradients are disabled')
@@ -995,15 +1078,37 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=
             row_plan = _row_plan(func, params, method, y0) if torch.is_grad_enabled() else (None, 'gradients are disabled')
             if lower is True and row_plan[0] is None:
                 raise ValueError('odeint_discrete(lower=True): the fused row-local sweep does not take this call: ' + row_plan[1])
-        out = _OdeintDiscreteLinear.apply(lin_plan, row_plan, func, fwd, method, options, t, tensor_input, len(params), *params, *ys)
+        rest = (func, fwd, method, options, t, tensor_input, len(params)) + tuple(params) + tuple(ys)
+        if mlp64 is not False:
+            if lin_plan[0] is None and (row_plan is None or row_plan[0] is None):
+                _mlp64_check(mlp64, func, params, method, tensor_input, ys, t.numel())
+            out = _OdeintDiscreteMlp64.apply(mlp64, None, None, lin_plan, row_plan, *rest)
+        else:
+            out = _OdeintDiscreteLinear.apply(lin_plan, row_plan, *rest)
         return out[0] if tensor_input else tuple(out)
     if lower is not False:
         row_plan = _row_plan(func, params, method, y0) if torch.is_grad_enabled() else (None, 'gradients are disabled')
         if lower is True and row_plan[0] is None:
             raise ValueError('odeint_discrete(lower=True): the fused row-local sweep does not take this call: ' + row_plan[1])
-        out = _OdeintDiscreteLowered.apply(row_plan, func, fwd, method, options, t, tensor_input, len(params), *params, *ys)
+        rest = (func, fwd, method, options, t, tensor_input, len(params)) + tuple(params) + tuple(ys)
+        if mlp64 is not False:
+            if row_plan[0] is None:
+                _mlp64_check(mlp64, func, params, method, tensor_input, ys, t.numel())
+            out = _OdeintDiscreteMlp64.apply(mlp64, None, None, None, row_plan, *rest)
+        else:
+            out = _OdeintDiscreteLowered.apply(row_plan, *rest)
         return out[0] if tensor_input else tuple(out)
-    out = _OdeintDiscrete.apply(func, fwd, method, options, t, tensor_input, len(params), *params, *ys)
+    rest = (func, fwd, method, options, t, tensor_input, len(params)) + tuple(params) + tuple(ys)
+    if mlp64 is not False:
+        n_pts = t.numel()
+        if step_size is not None:                        # a grid of its own: the backward sweeps the recomputed grid in segments
+            n_grid = int(_grid_plan(t, step_size, ys[0].dtype).grid.shape[0]) - 1
+            seg = _segments(n_grid, sum(y_.numel() * y_.element_size() for y_ in ys))
+            n_pts = seg[1] - seg[0] + 1
+        _mlp64_check(mlp64, func, params, method, tensor_input, ys, n_pts)
+        out = _OdeintDiscreteMlp64.apply(mlp64, None, None, None, None, *rest)
+    else:
+        out = _OdeintDiscrete.apply(*rest)
     return out[0] if tensor_input else tuple(out)
 
 
