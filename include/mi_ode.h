@@ -248,6 +248,20 @@ int mi_ode_advance(mi_ode_handle h, const double* t_out_host, int32_t n_out, voi
 /* AdaptiveStepsizeODESolver.integrate(t) (solvers.py:27-35): out_dev [T, batch*dim], out[0] = y0. */
 int mi_ode_integrate(mi_ode_handle h, const void* y0_dev, const double* t_host, int32_t T, void* out_dev,
                      mi_ode_stats* stats, void* stream);
+/* Per-trajectory step control (csrc/mi_ode_rows.h): the same call for a batch of INDEPENDENT systems.  Row i of out_dev is what
+ * mi_ode_integrate returns for y0[i] alone, bit for bit: every row has its own initial step, error ratio over its dim elements,
+ * accept / reject sequence, output cursor and dense output, max_num_steps and dt-underflow checks; t, rtol, atol and the other
+ * options of the handle are shared.  One launch for any batch size, no co-residency requirement.
+ *   h             an adaptive handle created for a trajectory-per-thread right-hand side (lotka_volterra, lorenz, 2 x 2 linear /
+ *                 cubic-linear without bias, a row-local plugin), one state tensor, one rank - anything else: MI_ODE_E_INVALID
+ *   rows_plugin   the table mi_ode_rows_plugin_get(dtype) of the plugin's rows shared object returned (csrc/mi_ode_rows_plugin.h)
+ *                 when the handle's right-hand side is a row-local plugin; NULL for the catalogue systems
+ *   row_stats_dev device [batch, 4] int64: attempts, accepted steps, function evaluations, status bits (MI_ODE_ST_*) of every row
+ *   stats         (nullable) n_attempts / n_accepted / n_rejected / nfe: the MAXIMUM over the rows; status: the OR over the rows
+ * A row that fails sets its own status and stops; the other rows are integrated to the end.  Returns the OR of the rows' status
+ * bits (>= 0) or an error (< 0). */
+int mi_ode_integrate_rows(mi_ode_handle h, const void* rows_plugin, const void* y0_dev, const double* t_host, int32_t T,
+                          void* out_dev, int64_t* row_stats_dev, mi_ode_stats* stats, void* stream);
 /* FixedGridODESolver.integrate(t) with grid = t (solvers.py:82-104); no host synchronisation inside. */
 int mi_ode_fixed_grid_integrate(mi_ode_handle h, const void* y0_dev, const double* t_host, int32_t T,
                                 void* out_dev, mi_ode_stats* stats, void* stream);

@@ -187,6 +187,8 @@ _PROTOS = {
     'mi_ode_advance': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_void_p]),
     'mi_ode_integrate': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p,
                                    C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_integrate_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.POINTER(Stats), C.c_void_p]),
     'mi_ode_fixed_grid_integrate': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p,
                                               C.POINTER(Stats), C.c_void_p]),
     'mi_ode_fixed_grid_integrate_on': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.c_int32,

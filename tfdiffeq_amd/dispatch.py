@@ -17,6 +17,7 @@ AUTO, STAGE, STEP, WHOLE = (FUSION[k] for k in ('auto', 'stage', 'step', 'whole'
 #        fused_coop       the cooperative whole-call kernel (a network outside the tile kernels' box, or a tableau they are not instantiated for)
 #        fused_tuple      rhs.PerComponent over one segmented (adaptive) or concatenated (fixed grid) buffer
 #        fused_multistep  the one-launch fixed-order / variable-order Adams kernels
+#        fused_rows       options['per_trajectory']: every row an integration of its own on k_rows_rowlocal (no fallback: refused or run)
 #        callable         graph_step.DeviceControlledRK: f as a callable, the controller on the device
 #        planes           the host loop over plane kernels
 # rhs: the DeviceRHS a fused engine is built from.  why: the predicate that decided.  told: a descriptor whose family has no kernel for
@@ -84,8 +85,66 @@ def device_controlled(y0, rows, *, quartic, force_planes, group, graph):
     return quartic or rows == 6
 
 
-def adaptive_rk(func, y0, rows, fsal, *, quartic=True, force_planes=False, group=False, fusion=AUTO, graph='auto'):
-    """The adaptive Runge-Kutta solvers.  rows, fsal: the tableau's shape; quartic: the dense output is the quartic through the midpoint."""
+ROWS_WHY = 'per-trajectory step control, one launch'
+ROWS_TABLEAUS = 'dopri5, tsit5, bosh3, dopri8 and adaptive_heun'
+
+
+def per_trajectory_option(options):
+    """(options without the key, True | False) for options['per_trajectory']; anything but True / False is a ValueError."""
+    opts = dict(options or {})
+    value = opts.pop('per_trajectory', False)
+    if value is not True and value is not False:
+        raise ValueError("options['per_trajectory'] must be True or False (got %r)" % (value,))
+    return (opts if options is not None else None), value
+
+
+def rows_method_refusal(solver_cls):
+    """'' when `solver_cls` is an adaptive Runge-Kutta solver, else why options['per_trajectory'] refuses it."""
+    from .solvers import _AdaptiveRKSolver                # (solvers imports this module)
+    if isinstance(solver_cls, type) and issubclass(solver_cls, _AdaptiveRKSolver):
+        return ''
+    return ('a fixed-grid or Adams method (%s): every row already takes the same steps on a fixed grid, and the Adams kernels have shared '
+            'control only - per-trajectory step control exists for %s' % (getattr(solver_cls, '__name__', solver_cls), ROWS_TABLEAUS))
+
+
+def rows_family_why(name, dim):
+    return ('a right-hand side on the matrix-core or cooperative kernels (%s, dim %s): f is evaluated by the threads of a workgroup '
+            'together there, and a barrier under per-lane control flow cannot be - per-trajectory control takes rhs.Lorenz, '
+            'rhs.LotkaVolterra, 2 x 2 rhs.Linear / rhs.CubicLinear, rhs.CustomRowLocal and lowered callables of at most 32 elements' % (name, dim))
+
+
+def rows_refusal(func, y0, rows, fsal, *, quartic=True, force_planes=False, group=False):
+    """'' when k_rows_rowlocal (csrc/mi_ode_rows.h) takes this call, else the reason options['per_trajectory'] is refused with.  Pure: reads
+    the descriptor behind `func`, shapes and dtypes - never the device."""
+    dev = getattr(func, 'device_rhs', None)
+    if getattr(func, 'per_component', False) or len(y0) != 1:
+        return ('a tuple state of several components / rhs.PerComponent: the components of a tuple share one step size by definition '
+                '(misc.py:250-287) - pass one [batch, dim] tensor')
+    if group:
+        return 'a sharded run (process_group): rows never communicate, so shard the batch yourself and call once per rank'
+    if force_planes:
+        return "options['force_plane_kernels'] asks for the host loop, which has shared control only"
+    if dev is None:
+        return ('a Python callable that was not lowered: only a right-hand side that runs on the trajectory-per-thread kernels can have '
+                'per-trajectory control')
+    y = y0[0]
+    if not getattr(dev, 'row_local', False) or not (isinstance(y, torch.Tensor) and y.dim() >= 1 and y.numel() > 0 and dev.supports(y)):
+        return rows_family_why(type(dev).__name__, getattr(dev, 'dim', None))
+    one_row = rows == 1 and not fsal
+    if not ((fsal and rows in (3, 13) and quartic) or (fsal and rows == 6) or (one_row and quartic)):
+        return 'a %d-row tableau the per-trajectory kernel is not instantiated for (it is for %s)' % (rows, ROWS_TABLEAUS)
+    return ''
+
+
+def adaptive_rk(func, y0, rows, fsal, *, quartic=True, force_planes=False, group=False, fusion=AUTO, graph='auto', per_trajectory=False):
+    """The adaptive Runge-Kutta solvers.  rows, fsal: the tableau's shape; quartic: the dense output is the quartic through the midpoint.
+    per_trajectory: every row of the batch is an integration of its own (k_rows_rowlocal) - or a ValueError: never shared control."""
+    if per_trajectory:
+        why = rows_refusal(func, y0, rows, fsal, quartic=quartic, force_planes=force_planes, group=group)
+        if why:
+            raise ValueError("options['per_trajectory'] refused: " + why)
+        return Route('fused_rows', func.device_rhs, ROWS_WHY)
+
     def host(why, told=None):
         ok = device_controlled(y0, rows, quartic=quartic, force_planes=force_planes, group=group, graph=graph)
         return Route('callable' if ok else 'planes', None, why, told)

@@ -2050,6 +2050,8 @@ class _GeneratedRHS(R.DeviceRHS):
     _plugin = R.CustomRowLocal._plugin
     hyper_source = R.CustomRowLocal.hyper_source          # (row-local programs only: the hypersolver kernels take one trajectory per thread)
     hyper_plugin = R.CustomRowLocal.hyper_plugin
+    rows_source = R.CustomRowLocal.rows_source            # (row-local programs only, likewise: the per-trajectory kernel)
+    rows_plugin = R.CustomRowLocal.rows_plugin
 
     def fill(self, rhs, dtype, device):
         keep = super(_GeneratedRHS, self).fill(rhs, dtype, device)

@@ -50,7 +50,17 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     of a device buffer the controller overwrites (clone it to keep it), and up to 64 blind replays past the end are no-ops on the
     device but were recorded with func inside.  A func that synchronises with the host or records autograd is detected and stays eager;
     options={'graph': False} turns the recording off, 'host' restores the loop with the controller on the host.
+
+    options={'per_trajectory': True} (adaptive Runge-Kutta methods, y0 [batch, dim], a trajectory-per-thread right-hand side): the rows are
+    independent problems - row i of the result is what odeint(func, y0[i:i+1], t, ...) returns, every row with its own initial step, error
+    ratio, accept / reject sequence and assertions, all in one launch (`odeint.last_stats['rows']`: per-row counts and status).  The default
+    is the reference's semantics: one error norm and one step size for the whole batch.  What the mode cannot take raises ValueError.
     """
+    if options is not None and 'per_trajectory' in options:
+        from .dispatch import per_trajectory_option
+        options, per_row = per_trajectory_option(options)     # (False: the call below, as if the key were absent)
+        if per_row:
+            return _odeint_per_trajectory(func, y0, t, rtol, atol, method, options)
     pre = None
     if _plain_callable_no_grad_state(func, y0):
         # A plain callable over a state that does not require grad: whether it has TRAINABLE inputs of its own is read off its trace - the
@@ -176,6 +186,76 @@ def _try_lower(func, y0, method, options):
     if not several:
         _warn_once('odeint: `func` runs as a Python callable between library kernels (not lowered onto the fused kernels: %s)' % why)
     return None, why
+
+
+def _per_trajectory_target(func, y0, method, options):
+    """What an options={'per_trajectory': True} call runs: (lowered callable | None for a DeviceRHS, the options with the key set).  Whatever
+    the per-trajectory kernel cannot take is refused with a ValueError that says why - decided from `func`, shapes, dtypes and options
+    alone (no device), shared with `odeint.plan`."""
+    import torch
+    from . import dispatch as D
+    from . import lower as _lower
+
+    def refuse(why):
+        raise ValueError("options['per_trajectory'] refused: " + why)
+    if method is None:
+        raise ValueError('cannot supply `options` without specifying `method`')
+    why = D.rows_method_refusal(SOLVERS[method])
+    if why:
+        refuse(why)
+    options = dict(options or {})
+    ys = tuple(y0) if isinstance(y0, (tuple, list)) else (y0,)
+    group, planes = options.get('process_group') is not None, bool(options.get('force_plane_kernels', False))
+    if len(ys) != 1 or getattr(func, 'per_component', False) or group or planes:
+        refuse(D.rows_refusal(func, ys, 6, True, group=group, force_planes=planes))
+    y = ys[0]
+    if not isinstance(y, torch.Tensor) or y.dtype not in (torch.float32, torch.float64) or y.numel() == 0:
+        refuse('the state must be one non-empty float32 / float64 tensor [batch, dim]')
+    grad = ('inputs that require grad: there is no gradient route for per-trajectory step control yet - call odeint_adjoint without the '
+            'option (shared control)')
+    if torch.is_grad_enabled() and (y.requires_grad or _wants_grad(func, y0)):
+        refuse(grad)
+    opts = dict(options, per_trajectory=True)
+    if getattr(func, 'stage_rhs', None) is not None:
+        refuse(D.rows_family_why(type(func).__name__, getattr(func, 'dim', None)))
+    if _descriptor(func):
+        opts.pop('lower', None)
+        return None, opts
+    if not callable(func):
+        refuse('`func` is neither a DeviceRHS nor a callable')
+    mode = opts.get('lower', 'auto')                      # (asking for per-trajectory control IS asking for the tracer: only the option itself declines)
+    if mode is False or mode == 'off':
+        refuse("options['lower'] is False: a Python callable reaches the per-trajectory kernel only as a lowered row program")
+    wrapped = func
+    if y is not y0:                                       # a one-component tuple: the tensor form of the same system
+        def wrapped(t_, y_, _f=func):
+            return _f(t_, (y_,))[0]
+    try:
+        low = _lower.lower(wrapped, y, method=method)
+    except _lower.TraceError as e:
+        refuse('the tracer refuses this callable (%s), and a Python callable has shared control only' % e)
+    except Exception as e:
+        refuse('tracing this callable failed (%s: %s), and a Python callable has shared control only' % (type(e).__name__, e))
+    if torch.is_grad_enabled() and any(isinstance(e['t'], torch.Tensor) and e['t'].requires_grad for e in low.trace.tensors):
+        refuse(grad)
+    if not getattr(low.rhs, 'row_local', False):
+        refuse(D.rows_family_why("a lowered '%s' program" % low.kind, low.dim))
+    return low, opts
+
+
+def _odeint_per_trajectory(func, y0, t, rtol, atol, method, options):
+    """options={'per_trajectory': True}: row i of the result is what odeint(func, y0[i:i+1], t, ...) returns - every row of a [batch, dim]
+    state with its own initial step, error ratio, accept / reject sequence, output cursor and assertions, all rows in ONE launch
+    (csrc/mi_ode_rows.h).  A DeviceRHS goes to its solver (whose route refuses the families the kernel cannot take); a Python callable
+    reaches the kernel as a lowered row program.  Never answered with shared control."""
+    low, opts = _per_trajectory_target(func, y0, method, options)
+    if low is not None:
+        return _run_lowered(low, func, y0, t, rtol, atol, method, opts)
+    tensor_input, f, state, tt = _check_inputs(func, y0, t)
+    solver = SOLVERS[method](f, state, rtol=rtol, atol=atol, **opts)
+    solution = solver.integrate(tt)
+    odeint.last_stats = getattr(solver, 'stats', {})
+    return solution[0] if tensor_input else solution
 
 
 def _run_lowered(low, func, y0, t, rtol, atol, method, options):

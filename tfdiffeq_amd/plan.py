@@ -107,6 +107,27 @@ def plan_rhs(rhs, y, solver, route, opts):
     return d
 
 
+def plan_rows(func, y0, rtol, atol, method, opts):
+    """options['per_trajectory']: the per-trajectory kernel (csrc/mi_ode_rows.h) - or the reason the call is refused with (a ValueError
+    at the call: shared control is never substituted)."""
+    from .odeint import SOLVERS, _per_trajectory_target
+    try:
+        low, run_opts = _per_trajectory_target(func, y0, method, opts)
+        f, state = (func, y0) if low is None else (low.rhs, (y0[0] if isinstance(y0, (tuple, list)) else y0).reshape(low.state_shape))
+        run_opts.pop('lower', None)
+        ys = (state,) if isinstance(state, torch.Tensor) else tuple(state)
+        solver = SOLVERS[method](_TupleFunc(f), ys, rtol=rtol, atol=atol, **run_opts)
+        route = solver.route()
+    except ValueError as e:
+        return {'engine': 'refused', 'kernel': None, 'launches': None, 'per_trajectory': True, 'why': str(e), 'lower': None}
+    y, rhs, S = ys[0], route.rhs, len(solver.tableau.alpha)
+    fam = D.family(rhs)
+    return {'engine': 'fused', 'kernel': 'k_rows_rowlocal<%s, %d, ..> (a trajectory per thread, any batch size, no grid hand-off)' % (TNAME[y.dtype], S),
+            'launches': 'one per call', 'why': D.ROWS_WHY, 'per_trajectory': True, 'family': FAMILY.get(fam, fam),
+            'state': '%d x %d %s' % (y.numel() // max(int(rhs.dim or 1), 1), rhs.dim, str(y.dtype).replace('torch.', '')),
+            'lower': None if low is None else {'lowered': True, 'kind': low.kind, 'dim': low.dim, 'batch_axes': low.trace.nb}}
+
+
 def plan(func, y0, t=None, rtol=1e-7, atol=1e-9, method=None, options=None):
     """What `odeint(func, y0, t, rtol, atol, method, options)` will run on.  A dict: engine ('fused' | 'callable' | 'plane kernels'),
     kernel, launches, why (the predicate that decided), family / state, and `lower` (how a Python callable was lowered, or why not)."""
@@ -114,6 +135,9 @@ def plan(func, y0, t=None, rtol=1e-7, atol=1e-9, method=None, options=None):
     from .odeint import LOWER_DEFAULT, SOLVERS       # (the submodule: the package exports the function under its name)
     method = method or 'dopri5'
     opts = dict(options or {})
+    opts, per_row = D.per_trajectory_option(opts)
+    if per_row:
+        return plan_rows(func, y0, rtol, atol, method, opts)
     mode = opts.pop('lower', LOWER_DEFAULT)
     tensor_input = isinstance(y0, torch.Tensor)
     ys = (y0,) if tensor_input else tuple(y0)

@@ -480,6 +480,24 @@ class CustomRowLocal(DeviceRHS):
             plugins[dtype] = hit
         return hit
 
+    def rows_source(self, dtype):
+        """The rows plugin of this system (csrc/mi_ode_rows_plugin.h): the same functor behind the per-trajectory kernel."""
+        return rows_source_of(self.source(dtype))
+
+    def rows_plugin(self, dtype):
+        """(library, address of the mi_ode_rows_plugin table) for `dtype`; compiled once, cached by source and header hash."""
+        plugins = self.__dict__.setdefault('_rows_plugins', {})
+        hit = plugins.get(dtype)
+        if hit is None:
+            from . import _plugin_build
+            lib = _plugin_build.build_and_load(self.rows_source(dtype))
+            table = lib.mi_ode_rows_plugin_get(N.dtype_code(dtype))
+            if not table:
+                raise N.NativeError('rows plugin exports no table for %s' % dtype)
+            hit = (lib, int(table))
+            plugins[dtype] = hit
+        return hit
+
 
 _DISCRETE_PLUGINS = {}
 
@@ -503,6 +521,14 @@ def hyper_source_of(rowlocal_source):
     """A row-local plugin translation unit (mi_ode_plugin.h) turned into the hyper plugin of the same functor."""
     src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_hyper_plugin.h"')
     return src.replace('MI_ODE_DEFINE_ROWLOCAL_PLUGIN(', 'MI_ODE_DEFINE_HYPER_PLUGIN(')
+
+
+def rows_source_of(rowlocal_source):
+    """A row-local plugin translation unit (mi_ode_plugin.h) turned into the rows plugin of the same functor (per-trajectory step control)."""
+    if 'MI_ODE_DEFINE_ROWLOCAL_PLUGIN(' not in rowlocal_source:
+        raise ValueError('not a row-local plugin translation unit: the per-trajectory kernel takes one trajectory per thread')
+    src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_rows_plugin.h"')
+    return src.replace('MI_ODE_DEFINE_ROWLOCAL_PLUGIN(', 'MI_ODE_DEFINE_ROWS_PLUGIN(')
 
 
 _COOP_TEMPLATE = """// generated by tfdiffeq_amd.rhs.CustomCoop - do not edit

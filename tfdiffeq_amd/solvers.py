@@ -339,6 +339,20 @@ class _FusedEngine(object):
         self._raise_for_status(rc)
         return out
 
+    def integrate_rows(self, t, y0=None, rows_plugin=None):
+        """Per-trajectory step control (mi_ode_integrate_rows): (solution, [batch, 4] int64 {attempts, accepted, nfe, status} per row on
+        the device, the OR of the rows' status bits).  rows_plugin: (library, table) of a plugin right-hand side's rows plugin."""
+        y0 = self._check_y0(y0)
+        arr, p = self._times(t)
+        T = arr.shape[0]
+        out = torch.empty((T,) + self.shape, dtype=self.dtype, device=self.device)
+        rows = torch.empty((self.batch, 4), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = N.check(self.lib.mi_ode_integrate_rows(self.h, C.c_void_p(rows_plugin[1] if rows_plugin is not None else 0), C.c_void_p(y0.data_ptr()),
+                                                        p, T, C.c_void_p(out.data_ptr()), C.c_void_p(rows.data_ptr()), C.byref(self.stats),
+                                                        self._stream()), 'mi_ode_integrate_rows')
+        return out, rows, rc
+
     def begin(self, t0, y0=None):
         y0 = self._check_y0(y0)
         with torch.cuda.device(self.device):
@@ -740,6 +754,10 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
         self._graph_attempt = None
         fusion = unused_kwargs.pop('fusion', 0)
         self._fusion = D.FUSION.get(fusion, fusion)
+        # every row of the batch an integration of its own (csrc/mi_ode_rows.h): its own initial step, error ratio, accept / reject
+        # sequence, output cursor and assertions - what one call per row y0[i:i+1] computes, in one launch.  False: the reference's
+        # semantics (one norm over the batch)
+        self._per_trajectory = D.per_trajectory_option({'per_trajectory': unused_kwargs.pop('per_trajectory', False)})[1]
         _handle_unused_kwargs(self, unused_kwargs)
         self.func = func
         self.y0 = y0
@@ -762,11 +780,13 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
 
     def route(self):
         """The engine this call is routed to (dispatch.Route), decided without running anything."""
-        return D.adaptive_rk(self.func, self.y0, len(self.tableau.alpha), _is_fsal_shaped(self.tableau), fusion=self._fusion, **self._options())
+        return D.adaptive_rk(self.func, self.y0, len(self.tableau.alpha), _is_fsal_shaped(self.tableau), fusion=self._fusion,
+                             per_trajectory=self._per_trajectory, **self._options())
 
     # -- fused engine ----------------------------------------------------------------------------
-    def _make_engine(self, route):
-        """The engine of a fused route, or None where mi_ode_create has no kernel for this call after all: dispatch.after(route)."""
+    def _make_engine(self, route, y_rows=None):
+        """The engine of a fused route, or None where mi_ode_create has no kernel for this call after all: dispatch.after(route).
+        y_rows: a state tensor in place of y0 (the one-row engine that words a failing row's assertion)."""
         rhs = route.rhs
         self._packed = _pack_components(self.y0, rhs.dim) if route.kind == 'fused_tuple' else None
         rtol0 = self.rtol if self.pooled_ratio else self.rtol[0]
@@ -776,6 +796,8 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
             from .misc import _convert_to_tensor
             first = float(_convert_to_tensor(self.first_step, dtype=np.float64))   # dopri5.py:77: float32 detour
         y = self.y0[0] if self._packed is None else self._packed[0]
+        if y_rows is not None:
+            y = y_rows
         seg_rows = None if self._packed is None else tuple(self._packed[1])
         seg_tols = None
         if seg_rows is not None and not self.pooled_ratio and \
@@ -811,6 +833,8 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
 
     def integrate(self, t):
         _assert_increasing(t)
+        if self._per_trajectory:
+            self.route()                                         # (a refusal is a ValueError of the call, whatever device y0 is on)
         for y_ in self.y0:
             N.require_gpu_tensor(y_, 'y0')
         route = self.route()
@@ -818,7 +842,32 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
         self.stats['route'] = route.kind                         # (as decided, whatever the run fell back to)
         return out
 
+    def _integrate_rows(self, route, t):
+        """options['per_trajectory']: k_rows_rowlocal, one launch - there is no other schedule, so nothing here falls back."""
+        rhs, y = route.rhs, self.y0[0]
+        eng = self._make_engine(route)
+        plugin = rhs.rows_plugin(y.dtype) if rhs.kind == N.RHS_PLUGIN else None
+        times = t.to(torch.float64).numpy()
+        out, rows, bits = eng.integrate_rows(times, y, plugin)
+        self.stats = dict(eng.stats.as_dict(), engine='k_rows_rowlocal: ' + D.ROWS_WHY, per_trajectory=True,
+                          rows={'n_attempts': rows[:, 0], 'n_accepted': rows[:, 1], 'nfe': rows[:, 2], 'status': rows[:, 3]})
+        if bits:
+            bad = torch.nonzero(rows[:, 3]).flatten().tolist()
+            first = bad[0]
+            # row i is what the call on y0[i:i+1] computes: that call words the assertion (the reference's message, with the row's own dt)
+            msg = N.status_message(int(rows[first, 3]))
+            row = y.reshape(-1, rhs.dim)[first:first + 1].contiguous()
+            try:
+                self._make_engine(route, row).integrate(times, row)
+            except AssertionError as e:
+                msg = str(e)
+            raise AssertionError('%s [per_trajectory: %d of %d rows failed; rows %s%s, the message is row %d\'s]' % (
+                msg, len(bad), int(rows.shape[0]), ', '.join(str(i) for i in bad[:8]), ', ...' if len(bad) > 8 else '', first))
+        return (out,)
+
     def _integrate_on(self, route, t):
+        if route.kind == 'fused_rows':
+            return self._integrate_rows(route, t)
         fused = route.kind in ('fused', 'fused_tuple', 'fused_coop')
         eng = self._make_engine(route) if fused else None
         if eng is not None and route.kind == 'fused_coop':
