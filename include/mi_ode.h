@@ -493,6 +493,42 @@ typedef struct mi_ode_discrete_row_desc {
 int mi_ode_discrete_row_sweep(const mi_ode_discrete_row_desc* desc, const mi_ode_rhs* rhs, const void* ys_dev, const void* grad_ys_dev,
                               void* grad_y0_out_dev, void* grad_theta_out_dev, mi_ode_stats* stats, void* stream);
 
+/* ---- (A-rows-adjoint) gradients of a per-trajectory solve (mi_ode_integrate_rows) for a row-local f with a generated vjp, ONE launch ---- */
+/* The reference's adjoint algorithm (adjoint.py:117-178) applied to every row of the batch ALONE (csrc/mi_ode_rows_adjoint.h): for
+ * k = T-1 .. 1 the row's dLd_cur_t = f(t_k, y_k) . g_k, then the adaptive integration of ITS tuple state (y [1, dim], adj_y [1, dim],
+ * adj_t [], adj_params [P]) from t_k to t_{k-1} with the reference's per-component control (one error ratio and one scalar tolerance per
+ * component, accepted if all ratios are <= 1), then adj_y += g_{k-1}.  A trajectory per lane; rows never interact inside the loops.
+ * rhs: MI_ODE_RHS_PLUGIN with `plugin` = what a rows-adjoint plugin's mi_ode_rows_adjoint_plugin_get(dtype) returned
+ * (csrc/mi_ode_rows_adjoint_plugin.h); scalars and w[0] as for the row-local plugin of the same callable.  fp32 or fp64,
+ * 2 dim + 1 + max(n_params, 1) <= 32, the FSAL shaped 6-row (dopri5) and 3-row (bosh3) tableaus.  The caller owns every buffer. */
+typedef struct mi_ode_adjoint_rows_desc {
+  int32_t dtype;              /* MI_ODE_F32 / MI_ODE_F64 */
+  int32_t n_times;            /* T >= 1 output times */
+  int64_t batch;
+  int32_t dim;                /* the plugin's */
+  int32_t n_params;           /* P: trainable elements, the plugin's */
+  int32_t order, init_order;  /* dopri5: 5, 4; bosh3: 3, 2 */
+  double rtol, atol;          /* adjoint_rtol / adjoint_atol: one scalar pair for the four components */
+  double safety, ifactor, dfactor;
+  int64_t max_num_steps;      /* <= 0: 2^31 - 1 */
+  mi_ode_tableau tableau;
+  const double* neg_t_dev;    /* device: the T output times, NEGATED (the backward solves run in the solver's time s = -t, misc.py:318-321) */
+  void* row_params_dev;       /* out [batch, max(P, 1)]: every row's own adj_params */
+  void* row_time_vjps_dev;    /* out [batch, T]: every row's own time vjps */
+  int64_t* row_counts_dev;    /* out [batch, 3, T - 1]: attempts, accepted steps, function evaluations of the interval t_k -> t_{k-1} at k - 1 */
+  int64_t* row_status_dev;    /* out [batch]: MI_ODE_ST_* bits of the row (an interval that ends with one ends the row) */
+  void* partials_dev;         /* workspace: ceil(batch / 256) * (max(P, 1) + T) elements of the state dtype */
+  void* ticket_dev;           /* one zeroed 32-bit word (left zero again) */
+} mi_ode_adjoint_rows_desc;
+/* ans_dev: the forward solution [T, batch, dim]; grad_ans_dev: the gradient of the loss with respect to it; grad_y0_out_dev [batch, dim];
+ * grad_params_out_dev [max(P, 1)] and grad_t_out_dev [T]: the rows summed in a fixed order (rows of a workgroup in row order, workgroups in
+ * order, by the last workgroup to arrive) - two calls give identical bits.  Enqueues one launch on `stream` and returns 0 without waiting,
+ * or a negative MI_ODE_E_* (MI_ODE_E_INVALID for a null / inconsistent argument or another table in rhs->plugin, MI_ODE_E_NODEVICE
+ * without a device); a failing row is reported in row_status_dev, not here. */
+int mi_ode_adjoint_rows(const mi_ode_adjoint_rows_desc* desc, const mi_ode_rhs* rhs, const void* ans_dev, const void* grad_ans_dev,
+                        void* grad_y0_out_dev, void* grad_params_out_dev, void* grad_t_out_dev, mi_ode_stats* stats, void* stream);
+int64_t mi_ode_adjoint_rows_sizeof(void);                 /* sizeof(mi_ode_adjoint_rows_desc), for a binding's layout check */
+
 /* ---- (A'''''') the same reverse sweep for the linear system f(y) = y W (+ b) on the matrix cores, ONE launch ------------------------ */
 /* The transpose of the fixed-grid map of MI_ODE_RHS_LINEAR (csrc/mi_ode_discrete_linear.h): Ybar_i = kbar_i W^T, Wbar += Y_i^T kbar_i,
  * bbar += sum_rows kbar_i.  fp32 or fp64, dim <= 128 (smaller dims run zero padded on the 16 / 32 / 64 / 128 wide instantiations), at most

@@ -107,6 +107,18 @@ class DiscreteRowDesc(C.Structure):
 DISCRETE_ROW_MAX_PARAMS, DISCRETE_ROW_THREADS, DISCRETE_ROW_MAX_GRID = 1024, 256, 1024
 
 
+class AdjointRowsDesc(C.Structure):
+    """mi_ode_adjoint_rows_desc: the adjoint of a per-trajectory solve of a lowered row-local callable in one launch."""
+    _fields_ = [('dtype', C.c_int32), ('n_times', C.c_int32), ('batch', C.c_int64), ('dim', C.c_int32), ('n_params', C.c_int32),
+                ('order', C.c_int32), ('init_order', C.c_int32), ('rtol', C.c_double), ('atol', C.c_double),
+                ('safety', C.c_double), ('ifactor', C.c_double), ('dfactor', C.c_double), ('max_num_steps', C.c_int64), ('tableau', Tableau),
+                ('neg_t_dev', C.c_void_p), ('row_params_dev', C.c_void_p), ('row_time_vjps_dev', C.c_void_p), ('row_counts_dev', C.c_void_p),
+                ('row_status_dev', C.c_void_p), ('partials_dev', C.c_void_p), ('ticket_dev', C.c_void_p)]
+
+
+ROWS_ADJOINT_MAX_AUG, ROWS_ADJOINT_THREADS = 32, 256
+
+
 class DiscreteLinearDesc(C.Structure):
     """mi_ode_discrete_linear_desc: the reverse sweep of a fixed-grid solve of f(y) = y W (+ b) in one launch, on the matrix cores."""
     _fields_ = [('dtype', C.c_int32), ('dim', C.c_int32), ('batch', C.c_int64), ('has_bias', C.c_int32), ('n_points', C.c_int32),
@@ -237,6 +249,9 @@ _PROTOS = {
     'mi_ode_discrete64_profile': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'mi_ode_discrete_row_sweep': (C.c_int, [C.POINTER(DiscreteRowDesc), C.POINTER(Rhs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_adjoint_rows': (C.c_int, [C.POINTER(AdjointRowsDesc), C.POINTER(Rhs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_adjoint_rows_sizeof': (C.c_int64, []),
     'mi_ode_discrete_linear_create': (C.c_int, [C.POINTER(DiscreteLinearDesc), C.POINTER(C.c_void_p)]),
     'mi_ode_discrete_linear_destroy': (C.c_int, [C.c_void_p]),
     'mi_ode_discrete_linear_sweep': (C.c_int, [C.c_void_p, C.POINTER(Rhs), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -336,6 +351,8 @@ def load():
         if lib.mi_ode_sizeof(which) != C.sizeof(st):
             raise NativeError('struct layout mismatch for %s: C %d vs ctypes %d'
                               % (st.__name__, lib.mi_ode_sizeof(which), C.sizeof(st)))
+    if lib.mi_ode_adjoint_rows_sizeof() != C.sizeof(AdjointRowsDesc):
+        raise NativeError('struct layout mismatch for AdjointRowsDesc: C %d vs ctypes %d' % (lib.mi_ode_adjoint_rows_sizeof(), C.sizeof(AdjointRowsDesc)))
     _lib = lib
     return lib
 

@@ -653,6 +653,19 @@ def odeint_adjoint(func, y0, t, rtol=1e-6, atol=1e-12, method=None, options=None
     """adjoint.py:183-224.  Gradients flow to y0, t and func's parameters."""
     if not isinstance(func, torch.nn.Module):
         raise ValueError('func is required to be an instance of torch.nn.Module')     # adjoint.py:187-188 (tf.keras.Model there)
+    if (options is not None and 'per_trajectory' in options) or (adjoint_options is not None and 'per_trajectory' in adjoint_options):
+        # options={'per_trajectory': True}: every row a solve of its own, forward AND backward (rows_adjoint.py, DESIGN.md 12.1) - or a
+        # ValueError.  False: the call below, as if the key were absent - it never reaches the routes below.
+        from .dispatch import per_trajectory_option
+        from . import rows_adjoint
+        if adjoint_options is not None and 'per_trajectory' in adjoint_options:
+            if adjoint_options.get('per_trajectory') != (options or {}).get('per_trajectory', False):
+                raise ValueError("options['per_trajectory'] belongs to `options`: the backward of a call follows its forward")
+            adjoint_options = per_trajectory_option(adjoint_options)[0]
+        options, per_row = per_trajectory_option(options)
+        if per_row:
+            return rows_adjoint.odeint_adjoint_rows(func, y0, t, rtol, atol, method, options, adjoint_method, adjoint_rtol, adjoint_atol,
+                                                    adjoint_options)
     if adjoint_method is None:
         adjoint_method = method
     if adjoint_rtol is None:
@@ -687,3 +700,12 @@ def odeint_adjoint(func, y0, t, rtol=1e-6, atol=1e-12, method=None, options=None
 
 
 odeint_adjoint.last_backward_stats = {}
+
+
+def _plan(*args, **kwargs):
+    from . import rows_adjoint
+    return rows_adjoint.plan(*args, **kwargs)
+
+
+_plan.__doc__ = 'What odeint_adjoint(..., options={\'per_trajectory\': True}) will run (rows_adjoint.plan).'
+odeint_adjoint.plan = _plan

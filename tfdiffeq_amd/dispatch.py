@@ -136,6 +136,27 @@ def rows_refusal(func, y0, rows, fsal, *, quartic=True, force_planes=False, grou
     return ''
 
 
+ROWS_ADJOINT_WHY = 'per-trajectory adjoint: every row its own augmented solve with per-component control, one launch'
+ROWS_ADJOINT_METHODS = ('dopri5', 'bosh3')
+
+
+def rows_adjoint_refusal(dim, n_params, adjoint_method, adjoint_rtol, adjoint_atol, adjoint_options):
+    """'' when k_rows_adjoint (csrc/mi_ode_rows_adjoint.h) takes the backward of an options['per_trajectory'] call whose forward
+    k_rows_rowlocal takes, else the reason odeint_adjoint refuses it with.  Pure: sizes, names and option keys only."""
+    n_aug = 2 * int(dim) + 1 + max(int(n_params), 1)
+    if n_aug > N.ROWS_ADJOINT_MAX_AUG:
+        return ('an augmented state of N_aug = 2 * %d + 1 + %d = %d elements per row: (y, adj_y, adj_t, adj_params) and its stage derivatives are '
+                'thread-private, the limit is %d' % (dim, max(int(n_params), 1), n_aug, N.ROWS_ADJOINT_MAX_AUG))
+    if adjoint_method not in ROWS_ADJOINT_METHODS:
+        return 'adjoint_method %r: the per-trajectory adjoint kernel is instantiated for %s' % (adjoint_method, ' and '.join(ROWS_ADJOINT_METHODS))
+    if isinstance(adjoint_rtol, (tuple, list)) or isinstance(adjoint_atol, (tuple, list)):
+        return 'tuple adjoint_rtol / adjoint_atol: the kernel takes one scalar pair for the four components'
+    extra = sorted(k for k in (adjoint_options or {}) if k != 'max_num_steps')
+    if extra:
+        return 'adjoint_options %s: the kernel\'s controller takes max_num_steps only (pass adjoint_options explicitly)' % extra
+    return ''
+
+
 def adaptive_rk(func, y0, rows, fsal, *, quartic=True, force_planes=False, group=False, fusion=AUTO, graph='auto', per_trajectory=False):
     """The adaptive Runge-Kutta solvers.  rows, fsal: the tableau's shape; quartic: the dense output is the quartic through the midpoint.
     per_trajectory: every row of the batch is an integration of its own (k_rows_rowlocal) - or a ValueError: never shared control."""

@@ -1362,9 +1362,10 @@ class _RowVjpCG(_RowCG):
     contribution to a trainable tensor goes to `acc.add(i, value)`: once per element from a local gN for tensors of up to WIDE elements,
     straight from the product's loop for wider ones.  Nodes that depend neither on y nor on a trainable tensor get no code."""
 
-    def __init__(self, tr):
+    def __init__(self, tr, with_t=False):
         super(_RowVjpCG, self).__init__(tr)
         self.par_off = {i: off for i, off, _n in vjp_params(tr)[0]}
+        self.with_t = with_t                             # also differentiate the `t` node: `tbar = (df/dt)^T kbar` (the adjoint's adj_t dynamics)
 
     def _g(self, m, i):
         return 'g%d[%s]' % (m.id, i)
@@ -1513,7 +1514,7 @@ class _RowVjpCG(_RowCG):
         for n in live:
             if n.is_bool:
                 continue
-            if n.op == 'y' or (n.op == 'ten' and n.attr in self.par_off) or any(m.id in need for m in n.args):
+            if n.op == 'y' or (n.op == 'ten' and n.attr in self.par_off) or (self.with_t and n.op == 't') or any(m.id in need for m in n.args):
                 need.add(n.id)
         self.need = need
         self.lines.append('// reverse')
@@ -1523,13 +1524,15 @@ class _RowVjpCG(_RowCG):
         if tr.out.id in need:
             for i in range(_prod(tr.tail)):
                 self.lines.append('g%d[%d] += kbar[%d];' % (tr.out.id, i, i))
-        ynode = None
+        ynode = tnode = None
         for n in reversed(live):
             if n.id not in need:
                 continue
             a = [val[x.id] for x in n.args]
             if n.op == 'y':
                 ynode = n
+            elif n.op == 't':
+                tnode = n                                # (only with_t puts it into `need`)
             elif n.op == 'ten':
                 if not self._direct(n):
                     off = self.par_off[n.attr]
@@ -1563,11 +1566,13 @@ class _RowVjpCG(_RowCG):
                 raise TraceError('more than %d statements for the evaluation and its reverse pass in one-trajectory-per-thread form' % MAX_ROW_STATEMENTS)
         for i in range(_prod(tr.tail)):
             self.lines.append('ybar[%d] = %s;' % (i, 'g%d[%d]' % (ynode.id, i) if ynode is not None else '(T)0'))
+        if self.with_t:
+            self.lines.append('tbar = %s;' % ('g%d[0]' % tnode.id if tnode is not None else '(T)0'))
         return '\n'.join(self.lines)
 
 
-def rowlocal_vjp_body(tr):
-    return _RowVjpCG(tr).vjp_body()
+def rowlocal_vjp_body(tr, with_t=False):
+    return _RowVjpCG(tr, with_t=with_t).vjp_body()
 
 
 _HOST_VJP_TEMPLATE = """// host build of a generated right-hand side and its vjp (tests: the same statements, compiled by g++)
@@ -1688,6 +1693,88 @@ def discrete_source(tr):
     """The discrete plugin of a row-local trace (csrc/mi_ode_discrete_plugin.h): the functor with operator() and vjp."""
     return _DISCRETE_TEMPLATE.format(dtype_macro='MI_ODE_PLUGIN_F32' if tr.dtype == torch.float32 else 'MI_ODE_PLUGIN_F64', dim=_prod(tr.tail),
                                      n_params=vjp_params(tr)[1], body=_indent(rowlocal_body(tr), 4), vjp=_indent(rowlocal_vjp_body(tr), 4))
+
+
+# ---------------------------------------------------------------------------------------------
+# the adjoint of a per-trajectory solve (csrc/mi_ode_rows_adjoint.h): f and its vjp with respect to y, t AND the trainable tensors
+# ---------------------------------------------------------------------------------------------
+_ADJOINT_TEMPLATE = """// generated by tfdiffeq_amd.lower from a traced Python callable: f and its vjp (y, t, parameters) for the per-trajectory adjoint - do not edit
+#define {dtype_macro} 1
+#include "mi_ode_rows_adjoint_plugin.h"
+namespace mi {{
+template <typename T>
+struct RhsUser {{
+  static constexpr int D = {dim};
+  static constexpr int P = {n_params};                     // grad-requiring elements: the range of acc.add's index
+  T p[8];
+  const T* cw;
+  __device__ explicit RhsUser(const RhsParams& r) : cw((const T*)r.w[0]) {{
+#pragma unroll
+    for (int i = 0; i < 8; ++i) p[i] = (T)r.s[i];
+  }}
+  __device__ __forceinline__ void operator()(T t, const T* y, T* k) const {{
+    (void)t; (void)cw;
+{body}
+  }}
+  template <class ACC>
+  __device__ __forceinline__ void vjp_t(T t, const T* y, const T* kbar, T* ybar, T& tbar, ACC& acc) const {{
+    (void)t; (void)cw; (void)acc; (void)kbar;
+{vjp}
+  }}
+}};
+}}  // namespace mi
+MI_ODE_DEFINE_ROWS_ADJOINT_PLUGIN(mi::RhsUser)
+"""
+
+_HOST_VJP_T_TEMPLATE = """// host build of a generated right-hand side and its vjp with respect to y, t and the parameters (tests: the same statements, g++)
+#include <cmath>
+using namespace std;
+template <typename T>
+struct RhsUser {{
+  static constexpr int D = {dim};
+  static constexpr int P = {n_params};
+  T p[8];
+  const T* cw;
+  RhsUser(const double* ps, const T* cw_) : cw(cw_) {{ for (int i = 0; i < 8; ++i) p[i] = (T)ps[i]; }}
+  void operator()(T t, const T* y, T* k) const {{
+    (void)t; (void)cw;
+{body}
+  }}
+  template <class ACC> void vjp_t(T t, const T* y, const T* kbar, T* ybar, T& tbar, ACC& acc) const {{
+    (void)t; (void)cw; (void)acc; (void)kbar;
+{vjp}
+  }}
+}};
+template <typename T> struct HostSinkT {{
+  T* g;
+  void add(int i, T v) {{ g[i] += v; }}
+}};
+template <typename T> static void vjpt_(T t, const T* y, const T* kbar, T* ybar, T* tbar, T* theta_bar, const double* ps, const T* cw) {{
+  RhsUser<T> f(ps, cw);
+  HostSinkT<T> acc{{theta_bar}};
+  f.vjp_t(t, y, kbar, ybar, *tbar, acc);
+}}
+extern "C" void vjpt_f64(double t, const double* y, const double* kbar, double* ybar, double* tbar, double* theta_bar, const double* ps, const double* cw) {{
+  vjpt_<double>(t, y, kbar, ybar, tbar, theta_bar, ps, cw);
+}}
+extern "C" void vjpt_f32(float t, const float* y, const float* kbar, float* ybar, float* tbar, float* theta_bar, const double* ps, const float* cw) {{
+  vjpt_<float>(t, y, kbar, ybar, tbar, theta_bar, ps, cw);
+}}
+"""
+
+
+def adjoint_source(tr):
+    """The rows-adjoint plugin of a row-local trace (csrc/mi_ode_rows_adjoint_plugin.h): the functor with operator() and vjp_t - the vjp
+    of discrete_source plus the rule for the `t` node (`tbar`), generated only here."""
+    return _ADJOINT_TEMPLATE.format(dtype_macro='MI_ODE_PLUGIN_F32' if tr.dtype == torch.float32 else 'MI_ODE_PLUGIN_F64', dim=_prod(tr.tail),
+                                    n_params=vjp_params(tr)[1], body=_indent(rowlocal_body(tr), 4), vjp=_indent(rowlocal_vjp_body(tr, with_t=True), 4))
+
+
+def host_vjp_t_source(tr):
+    """adjoint_source's functor as host code (the CPU tests compile it with g++, alone or under csrc/mi_ode_rows_adjoint_core.h):
+    `vjpt_f64 / vjpt_f32(t, y, kbar, ybar, tbar, theta_bar, ps, cw)` write ybar and *tbar and add into theta_bar."""
+    return _HOST_VJP_T_TEMPLATE.format(dim=_prod(tr.tail), n_params=vjp_params(tr)[1], body=_indent(rowlocal_body(tr), 4),
+                                       vjp=_indent(rowlocal_vjp_body(tr, with_t=True), 4))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -188,10 +188,11 @@ def _try_lower(func, y0, method, options):
     return None, why
 
 
-def _per_trajectory_target(func, y0, method, options):
+def _per_trajectory_target(func, y0, method, options, _adjoint=False):
     """What an options={'per_trajectory': True} call runs: (lowered callable | None for a DeviceRHS, the options with the key set).  Whatever
     the per-trajectory kernel cannot take is refused with a ValueError that says why - decided from `func`, shapes, dtypes and options
-    alone (no device), shared with `odeint.plan`."""
+    alone (no device), shared with `odeint.plan`.  _adjoint: the caller is odeint_adjoint's per-trajectory route (rows_adjoint.py), which
+    has a gradient route of its own - the only caller for which inputs that require grad are not refused."""
     import torch
     from . import dispatch as D
     from . import lower as _lower
@@ -211,9 +212,9 @@ def _per_trajectory_target(func, y0, method, options):
     y = ys[0]
     if not isinstance(y, torch.Tensor) or y.dtype not in (torch.float32, torch.float64) or y.numel() == 0:
         refuse('the state must be one non-empty float32 / float64 tensor [batch, dim]')
-    grad = ('inputs that require grad: there is no gradient route for per-trajectory step control yet - call odeint_adjoint without the '
-            'option (shared control)')
-    if torch.is_grad_enabled() and (y.requires_grad or _wants_grad(func, y0)):
+    grad = ('inputs that require grad: plain odeint has no gradient route for per-trajectory step control - call odeint_adjoint with the option '
+            '(a torch.nn.Module the tracer lowers: every row its own adjoint solve), or odeint_adjoint without the option (shared control)')
+    if not _adjoint and torch.is_grad_enabled() and (y.requires_grad or _wants_grad(func, y0)):
         refuse(grad)
     opts = dict(options, per_trajectory=True)
     if getattr(func, 'stage_rhs', None) is not None:
@@ -236,7 +237,7 @@ def _per_trajectory_target(func, y0, method, options):
         refuse('the tracer refuses this callable (%s), and a Python callable has shared control only' % e)
     except Exception as e:
         refuse('tracing this callable failed (%s: %s), and a Python callable has shared control only' % (type(e).__name__, e))
-    if torch.is_grad_enabled() and any(isinstance(e['t'], torch.Tensor) and e['t'].requires_grad for e in low.trace.tensors):
+    if not _adjoint and torch.is_grad_enabled() and any(isinstance(e['t'], torch.Tensor) and e['t'].requires_grad for e in low.trace.tensors):
         refuse(grad)
     if not getattr(low.rhs, 'row_local', False):
         refuse(D.rows_family_why("a lowered '%s' program" % low.kind, low.dim))

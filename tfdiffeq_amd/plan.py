@@ -128,9 +128,14 @@ def plan_rows(func, y0, rtol, atol, method, opts):
             'lower': None if low is None else {'lowered': True, 'kind': low.kind, 'dim': low.dim, 'batch_axes': low.trace.nb}}
 
 
-def plan(func, y0, t=None, rtol=1e-7, atol=1e-9, method=None, options=None):
+def plan(func, y0, t=None, rtol=1e-7, atol=1e-9, method=None, options=None, adjoint=False):
     """What `odeint(func, y0, t, rtol, atol, method, options)` will run on.  A dict: engine ('fused' | 'callable' | 'plane kernels'),
-    kernel, launches, why (the predicate that decided), family / state, and `lower` (how a Python callable was lowered, or why not)."""
+    kernel, launches, why (the predicate that decided), family / state, and `lower` (how a Python callable was lowered, or why not).
+    adjoint=True (with options['per_trajectory']): what `odeint_adjoint` runs for the same arguments - the per-trajectory adjoint kernel, or
+    engine 'refused' with the reason (`odeint_adjoint.plan`, which also takes the adjoint_* arguments)."""
+    if adjoint:
+        from . import rows_adjoint
+        return rows_adjoint.plan(func, y0, t, rtol=rtol, atol=atol, method=method, options=options)
     from . import lower as L
     from .odeint import LOWER_DEFAULT, SOLVERS       # (the submodule: the package exports the function under its name)
     method = method or 'dopri5'

@@ -517,6 +517,25 @@ def discrete_plugin(source, dtype):
     return hit
 
 
+_ROWS_ADJOINT_PLUGINS = {}
+
+
+def rows_adjoint_plugin(source, dtype):
+    """(library, address of the mi_ode_rows_adjoint_plugin table) of a rows-adjoint plugin translation unit (lower.adjoint_source:
+    csrc/mi_ode_rows_adjoint_plugin.h, f and its generated vjp behind the per-trajectory adjoint kernel); compiled once, cached by source
+    and header hash."""
+    hit = _ROWS_ADJOINT_PLUGINS.get((source, dtype))
+    if hit is None:
+        from . import _plugin_build
+        lib = _plugin_build.build_and_load(source)
+        table = lib.mi_ode_rows_adjoint_plugin_get(N.dtype_code(dtype))
+        if not table:
+            raise N.NativeError('rows-adjoint plugin exports no table for %s' % dtype)
+        hit = (lib, table)
+        _ROWS_ADJOINT_PLUGINS[(source, dtype)] = hit
+    return hit
+
+
 def hyper_source_of(rowlocal_source):
     """A row-local plugin translation unit (mi_ode_plugin.h) turned into the hyper plugin of the same functor."""
     src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_hyper_plugin.h"')
