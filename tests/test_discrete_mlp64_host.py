@@ -116,3 +116,84 @@ def test_the_float64_engines_have_their_own_cache_and_are_released(monkeypatch):
     assert D._ENGINES == before                              # the float32 cache is another one
     tfdiffeq_amd.clear_engine_cache()
     assert not D._ENGINES64 and all(e.closed for e in Fake.made)
+
+
+def _recording_fused_plan(monkeypatch):
+    """_fused_plan stands aside and records the length of the trajectory it was asked to plan for; mlp64=True then raises with its reason."""
+    seen = []
+
+    def fused_plan(func, params, method, tensor_input, like, mlp64=False):
+        seen.append(int(like.shape[0]))
+        return None, 'recorded'
+    monkeypatch.setattr(D, '_fused_plan', fused_plan)
+    monkeypatch.setattr(N, 'require_gpu_tensor', lambda *a, **k: None)
+    return seen
+
+
+def test_the_float64_check_plans_for_the_points_of_t_on_the_default_grid(monkeypatch):
+    seen = _recording_fused_plan(monkeypatch)
+    func = models.ODEFunc(4, 8, non_linearity='tanh').double()
+    y0 = torch.zeros(3, 4, dtype=torch.float64, requires_grad=True)
+    with pytest.raises(ValueError, match='recorded'):
+        odeint_discrete(func, y0, torch.linspace(0., 1., 3, dtype=torch.float64), method='rk4', mlp64=True)
+    assert seen == [3]
+
+
+@pytest.mark.parametrize('lower', (False, 'auto'))
+def test_the_float64_check_plans_for_the_segment_the_backward_sweeps_on_a_grid_of_its_own(monkeypatch, lower):
+    """t has 2 points, step_size 1 / 8 gives 8 grid steps: the backward sweeps one segment of 9 grid states, whatever other switch is
+    on (models.ODEFunc is a callable the row planner refuses: it does not lower to a row-local program)."""
+    seen = _recording_fused_plan(monkeypatch)
+    func = models.ODEFunc(4, 8, non_linearity='tanh').double()
+    y0 = torch.zeros(3, 4, dtype=torch.float64, requires_grad=True)
+    assert D._row_plan(func, tuple(func.parameters()), 'rk4', y0.detach())[0] is None
+    with pytest.raises(ValueError, match='recorded'):
+        odeint_discrete(func, y0, torch.tensor([0., 1.], dtype=torch.float64), method='rk4', options={'step_size': 1 / 8}, own_grid=True,
+                        mlp64=True, lower=lower)
+    assert seen == [9]
+
+
+_MLP_KEY = lambda n: (33, 3, 5, 'rk4', n, 'cuda:0', 0, True)                                  # noqa: E731
+CACHES = {
+    '_cached_engine': ('_FusedDiscreteEngine', '_ENGINES', _MLP_KEY, True),
+    '_cached_engine64': ('_FusedDiscreteEngine64', '_ENGINES64', _MLP_KEY, True),
+    '_cached_linear_engine': ('_FusedLinearEngine', '_LINEAR_ENGINES', lambda n: (17, 6, True, 'heun', n, 'cuda:0', torch.float64), False),
+    '_cached_linear_grid_engine': ('_FusedLinearGridEngine', '_LINEAR_ENGINES', lambda n: (17, 6, True, 'heun', n, 3, 'cuda:0', torch.float64), False),
+}
+
+
+@pytest.mark.parametrize('name', sorted(CACHES))
+def test_the_cache_contract_of_every_engine(monkeypatch, name):
+    """A hit returns the same object; the fifth key evicts the oldest; a create that raises evicts nothing; an evicted MLP engine is
+    closed, an evicted linear engine is only dropped (a pending plan may still hold it)."""
+    engine, cache, key, closes = CACHES[name]
+
+    class Fake(object):
+        made, fail = [], False
+
+        def __init__(self, *args):
+            if Fake.fail:
+                raise N.NativeError('no memory')
+            self.args, self.closed = args, False
+            Fake.made.append(self)
+
+        def close(self):
+            self.closed = True
+    monkeypatch.setattr(D, engine, Fake)                     # (the class is looked up when the cache creates)
+    monkeypatch.setattr(D, cache, {})
+    cached = getattr(D, name)
+    first = cached(*key(5))
+    assert cached(*key(5)) is first and len(Fake.made) == 1 and first.args == key(5)
+    for n in (6, 7, 8):
+        cached(*key(n))
+    assert len(getattr(D, cache)) == 4 and not first.closed
+    Fake.fail = True
+    before = dict(getattr(D, cache))
+    with pytest.raises(N.NativeError):
+        cached(*key(9))
+    assert getattr(D, cache) == before and list(getattr(D, cache)) == list(before) and not any(e.closed for e in Fake.made)
+    Fake.fail = False
+    fifth = cached(*key(9))
+    held = list(getattr(D, cache).values())
+    assert len(held) == 4 and first not in held and held[-1] is fifth and held[:3] == Fake.made[1:4]
+    assert first.closed is closes and not any(e.closed for e in Fake.made[1:])

@@ -34,6 +34,11 @@ them (solvers.py:86-115).  There the backward recomputes the grid states from y0
 GRID_BYTES), places the output gradients on the grid (_grid_plan) and runs the engines above; the linear system has a kernel mode that
 does all of it in ONE launch without a stored trajectory ('fused linear sweep (own grid)', GRID_KERNEL).  Adaptive solves over a recorded
 step sequence, the multistep family, grid_constructor and eps != 0 are not covered: they raise ValueError and name `odeint_adjoint`.
+
+Layout: the engines that own a native handle (_FusedDiscreteEngine / ...64, _FusedLinearEngine, _FusedLinearGridEngine) share _SweepEngine
+(create, close, the status of a sweep) and the size-4 cache rule of _cached.  `odeint_discrete` plans a call ONCE, in the order own-grid
+linear kernel, linear sweep, row-local sweep, float64 mlp check - each for the trajectory length the backward will sweep - and hands the
+outcome to _OdeintDiscretePlanned as one _Plans record; with every switch off it calls plain _OdeintDiscrete.
 """
 import collections
 import ctypes as C
@@ -165,27 +170,22 @@ def generic_sweep(func, params, ys, t, grad_ys, method):
     return lam, gp
 
 
-class _FusedDiscreteEngine(object):
-    """Owns one mi_ode_discrete handle: the reverse sweep of `n_points - 1` steps of `method` for a [batch, dim] state in `dtype` and the
-    dim -> hidden -> hidden -> dim MLP (time_dependent: (1 + dim) -> hidden, the first layer sees concat([t, x])), one launch."""
-    dtype = torch.float32
-    _create, _destroy, _num_params, _sweep = 'mi_ode_discrete_create_td', 'mi_ode_discrete_destroy', 'mi_ode_discrete_num_params', 'mi_ode_discrete_sweep'
+class _SweepEngine(object):
+    """Owns one handle of a one-launch sweep: the library, the device, the descriptor, the stats of the last sweep.  A subclass names its
+    create and destroy symbols, fills its descriptor and says what a sweep passes."""
+    _create = _destroy = None
 
-    def __init__(self, batch, dim, hidden, method, n_points, device, chunk_tiles=0, time_dependent=False):
+    def _open(self, device, desc, method, *create_args):
+        """The handle of `desc` (its tableau: `method`'s) on `device`; create_args go between the descriptor and the handle."""
         from .solvers import _fill_tableau
         self.lib = N.load()
         self.device = torch.device(device)
-        d = N.DiscreteDesc()
-        d.batch, d.dim, d.hidden = int(batch), int(dim), int(hidden)
-        _fill_tableau(d.tableau, TABLEAUS[method], None)
-        d.n_points, d.chunk_tiles = int(n_points), int(chunk_tiles)
-        self.desc = d
+        _fill_tableau(desc.tableau, TABLEAUS[method], None)
+        self.desc = desc
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            N.check(getattr(self.lib, self._create)(C.byref(d), 1 if time_dependent else 0, C.byref(h)), self._create)
+            N.check(getattr(self.lib, self._create)(C.byref(desc), *(create_args + (C.byref(h),))), self._create)
         self.h = h
-        self.batch, self.dim, self.n_points, self.time_dependent = int(batch), int(dim), int(n_points), bool(time_dependent)
-        self.n_params = int(getattr(self.lib, self._num_params)(h))
         self.stats = N.Stats()
 
     def close(self):
@@ -199,36 +199,64 @@ class _FusedDiscreteEngine(object):
         except Exception:
             pass
 
-    def sweep(self, mlp, t, ys, grad_ys):
-        """(grad_y0 [batch, dim], grad_theta [P] in canonical order) from the forward solution and its gradient, both [N, batch, dim]."""
-        r = N.Rhs()
-        keep = mlp.fill(r, self.dtype, self.device)
-        ys, grad_ys = ys.contiguous(), grad_ys.contiguous()
-        g_y0 = torch.empty(self.batch, self.dim, dtype=self.dtype, device=self.device)
-        g_th = torch.empty(self.n_params, dtype=self.dtype, device=self.device)
-        tt = (C.c_double * self.n_points)(*[float(v) for v in t])
+    def _run(self, name, args, value):
+        """The sweep `name` of this handle with `args`, the stats and the stream: `value`, or HandoffTimeout / AssertionError for the
+        status it returned."""
         with torch.cuda.device(self.device):
-            rc = N.check(getattr(self.lib, self._sweep)(self.h, C.byref(r), tt, ys.data_ptr(), grad_ys.data_ptr(), g_y0.data_ptr(), g_th.data_ptr(),
-                                                        C.byref(self.stats), N.stream_ptr(self.device)), self._sweep)
-        del keep
+            rc = N.check(getattr(self.lib, name)(self.h, *(tuple(args) + (C.byref(self.stats), N.stream_ptr(self.device)))), name)
         if rc != 0:
             from .adjoint import HandoffTimeout
             if rc & N.ST_SYNC_TIMEOUT:
                 raise HandoffTimeout(N.status_message(rc))
             raise AssertionError(N.status_message(rc))
-        return g_y0, g_th
+        return value
+
+
+def _cached(cache, key, make, close_on_evict):
+    """The engine of `key` in `cache`, four cached at most, the oldest evicted - only after a successful make(): a refusal must not cost
+    live engines.  close_on_evict: the evicted engine is closed; otherwise only the cache's reference is dropped."""
+    eng = cache.get(key)
+    if eng is None:
+        eng = make()
+        while len(cache) >= 4:
+            old = cache.pop(next(iter(cache)))
+            if close_on_evict:
+                old.close()
+        cache[key] = eng
+    return eng
+
+
+class _FusedDiscreteEngine(_SweepEngine):
+    """Owns one mi_ode_discrete handle: the reverse sweep of `n_points - 1` steps of `method` for a [batch, dim] state in `dtype` and the
+    dim -> hidden -> hidden -> dim MLP (time_dependent: (1 + dim) -> hidden, the first layer sees concat([t, x])), one launch."""
+    dtype = torch.float32
+    _create, _destroy, _num_params, _sweep = 'mi_ode_discrete_create_td', 'mi_ode_discrete_destroy', 'mi_ode_discrete_num_params', 'mi_ode_discrete_sweep'
+
+    def __init__(self, batch, dim, hidden, method, n_points, device, chunk_tiles=0, time_dependent=False):
+        d = N.DiscreteDesc()
+        d.batch, d.dim, d.hidden = int(batch), int(dim), int(hidden)
+        d.n_points, d.chunk_tiles = int(n_points), int(chunk_tiles)
+        self._open(device, d, method, 1 if time_dependent else 0)
+        self.batch, self.dim, self.n_points, self.time_dependent = int(batch), int(dim), int(n_points), bool(time_dependent)
+        self.n_params = int(getattr(self.lib, self._num_params)(self.h))
+
+    def sweep(self, mlp, t, ys, grad_ys):
+        """(grad_y0 [batch, dim], grad_theta [P] in canonical order) from the forward solution and its gradient, both [N, batch, dim]."""
+        r = N.Rhs()
+        keep = mlp.fill(r, self.dtype, self.device)          # (the tensors the descriptor points into live to the end of the call)
+        ys, grad_ys = ys.contiguous(), grad_ys.contiguous()
+        g_y0 = torch.empty(self.batch, self.dim, dtype=self.dtype, device=self.device)
+        g_th = torch.empty(self.n_params, dtype=self.dtype, device=self.device)
+        tt = (C.c_double * self.n_points)(*[float(v) for v in t])
+        out = self._run(self._sweep, (C.byref(r), tt, ys.data_ptr(), grad_ys.data_ptr(), g_y0.data_ptr(), g_th.data_ptr()), (g_y0, g_th))
+        del keep
+        return out
 
 
 def _cached_engine(batch, dim, hidden, method, n_points, device, chunk_tiles=0, time_dependent=False):
+    """The float32 MLP engine (shape first in the key, the chunk last).  Eviction closes: the plan is formed in backward, around its sweep."""
     key = (batch, dim, hidden, method, n_points, device, bool(time_dependent), chunk_tiles)
-    eng = _ENGINES.get(key)
-    if eng is None:
-        # (evict only after a successful create: a refusal must not cost live engines)
-        eng = _FusedDiscreteEngine(batch, dim, hidden, method, n_points, device, chunk_tiles, time_dependent)
-        while len(_ENGINES) >= 4:
-            _ENGINES.pop(next(iter(_ENGINES))).close()
-        _ENGINES[key] = eng
-    return eng
+    return _cached(_ENGINES, key, lambda: _FusedDiscreteEngine(batch, dim, hidden, method, n_points, device, chunk_tiles, time_dependent), True)
 
 
 class _FusedDiscreteEngine64(_FusedDiscreteEngine):
@@ -245,15 +273,9 @@ class _FusedDiscreteEngine64(_FusedDiscreteEngine):
 
 
 def _cached_engine64(batch, dim, hidden, method, n_points, device, chunk_tiles=0, time_dependent=False):
-    """_cached_engine for the float64 kernel: the same size-4 eviction, the dtype in the key (shape first, the chunk last)."""
+    """_cached_engine for the float64 kernel: a cache of its own, the dtype in the key."""
     key = (batch, dim, hidden, method, n_points, device, 'float64', bool(time_dependent), chunk_tiles)
-    eng = _ENGINES64.get(key)
-    if eng is None:
-        eng = _FusedDiscreteEngine64(batch, dim, hidden, method, n_points, device, chunk_tiles, time_dependent)
-        while len(_ENGINES64) >= 4:
-            _ENGINES64.pop(next(iter(_ENGINES64))).close()
-        _ENGINES64[key] = eng
-    return eng
+    return _cached(_ENGINES64, key, lambda: _FusedDiscreteEngine64(batch, dim, hidden, method, n_points, device, chunk_tiles, time_dependent), True)
 
 
 def clear_engines():
@@ -315,36 +337,33 @@ def _fused_plan(func, params, method, tensor_input, like, mlp64=False):
     return (eng, mlp), ''
 
 
-class _FusedLinearEngine(object):
+def _linear_io(eng, W, b):
+    """What a sweep of f(y) = y W (+ b) on `eng` passes and returns: (the descriptor, the contiguous W and b it points into, (g_y0
+    [batch, dim], g_w [dim, dim] in W's [in, out] layout, g_b [dim] or None)).  W, b: device tensors in the state dtype, read now."""
+    r = N.Rhs()
+    r.kind, r.sign, r.hidden = N.RHS_LINEAR, 1.0, 0
+    W = W.contiguous()
+    r.w[0] = W.data_ptr()
+    if b is not None:
+        b = b.contiguous()
+        r.b[0] = b.data_ptr()
+    g_y0 = torch.empty(eng.batch, eng.dim, dtype=eng.dtype, device=eng.device)
+    g_w = torch.empty(eng.dim, eng.dim, dtype=eng.dtype, device=eng.device)
+    g_b = torch.empty(eng.dim, dtype=eng.dtype, device=eng.device) if b is not None else None
+    return r, (W, b), (g_y0, g_w, g_b)
+
+
+class _FusedLinearEngine(_SweepEngine):
     """Owns one mi_ode_discrete_linear handle: the reverse sweep of `n_points - 1` steps of `method` for a [batch, dim] state and
     f(y) = y W (+ b), one launch."""
+    _create, _destroy = 'mi_ode_discrete_linear_create', 'mi_ode_discrete_linear_destroy'
 
     def __init__(self, batch, dim, has_bias, method, n_points, device, dtype):
-        from .solvers import _fill_tableau
-        self.lib = N.load()
-        self.device = torch.device(device)
         self.dtype = dtype
         d = N.DiscreteLinearDesc()
         d.dtype, d.dim, d.batch, d.has_bias, d.n_points = N.dtype_code(dtype), int(dim), int(batch), int(bool(has_bias)), int(n_points)
-        _fill_tableau(d.tableau, TABLEAUS[method], None)
-        self.desc = d
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            N.check(self.lib.mi_ode_discrete_linear_create(C.byref(d), C.byref(h)), 'mi_ode_discrete_linear_create')
-        self.h = h
+        self._open(device, d, method)
         self.batch, self.dim, self.n_points, self.has_bias = int(batch), int(dim), int(n_points), bool(has_bias)
-        self.stats = N.Stats()
-
-    def close(self):
-        if getattr(self, 'h', None):
-            self.lib.mi_ode_discrete_linear_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def profile(self):
         """{'grid', 'sweep_us', 'store_us', 'fold_us'} of the last sweep: workgroup 0's clock over the tile sweep (all steps, the weight-gradient
@@ -356,73 +375,31 @@ class _FusedLinearEngine(object):
     def sweep(self, W, b, t, ys, grad_ys):
         """(grad_y0 [batch, dim], grad_W [dim, dim] in W's [in, out] layout, grad_b [dim] or None) from the forward solution and its
         gradient, both [N, batch, dim].  W, b: device tensors in the state dtype, read now (nothing is cached between calls)."""
-        r = N.Rhs()
-        r.kind, r.sign, r.hidden = N.RHS_LINEAR, 1.0, 0
-        W = W.contiguous()
-        r.w[0] = W.data_ptr()
-        if b is not None:
-            b = b.contiguous()
-            r.b[0] = b.data_ptr()
+        r, _keep, (g_y0, g_w, g_b) = _linear_io(self, W, b)
         ys, grad_ys = ys.contiguous(), grad_ys.contiguous()
-        g_y0 = torch.empty(self.batch, self.dim, dtype=self.dtype, device=self.device)
-        g_w = torch.empty(self.dim, self.dim, dtype=self.dtype, device=self.device)
-        g_b = torch.empty(self.dim, dtype=self.dtype, device=self.device) if b is not None else None
         tt = (C.c_double * self.n_points)(*[float(v) for v in t])
-        with torch.cuda.device(self.device):
-            rc = N.check(self.lib.mi_ode_discrete_linear_sweep(self.h, C.byref(r), tt, ys.data_ptr(), grad_ys.data_ptr(), g_y0.data_ptr(), g_w.data_ptr(),
-                                                               None if g_b is None else g_b.data_ptr(), C.byref(self.stats),
-                                                               N.stream_ptr(self.device)), 'mi_ode_discrete_linear_sweep')
-        if rc != 0:
-            from .adjoint import HandoffTimeout
-            if rc & N.ST_SYNC_TIMEOUT:
-                raise HandoffTimeout(N.status_message(rc))
-            raise AssertionError(N.status_message(rc))
-        return g_y0, g_w, g_b
+        return self._run('mi_ode_discrete_linear_sweep', (C.byref(r), tt, ys.data_ptr(), grad_ys.data_ptr(), g_y0.data_ptr(), g_w.data_ptr(),
+                                                          None if g_b is None else g_b.data_ptr()), (g_y0, g_w, g_b))
 
 
 def _cached_linear_engine(*key):
     """The engine of `key`, four cached at most.  The plan of a call holds its engine from the call to its backward, so eviction (and
     clear_engines) only drops the cache's reference: the handle is destroyed when the last pending plan lets go of it (__del__)."""
-    eng = _LINEAR_ENGINES.get(key)
-    if eng is None:
-        eng = _FusedLinearEngine(*key)                   # (evict only after a successful create: a refusal must not cost live engines)
-        while len(_LINEAR_ENGINES) >= 4:
-            _LINEAR_ENGINES.pop(next(iter(_LINEAR_ENGINES)))
-        _LINEAR_ENGINES[key] = eng
-    return eng
+    return _cached(_LINEAR_ENGINES, key, lambda: _FusedLinearEngine(*key), False)
 
 
-class _FusedLinearGridEngine(object):
+class _FusedLinearGridEngine(_SweepEngine):
     """Owns one mi_ode_discrete_linear_grid handle: the reverse sweep of `n_steps` grid steps of `method` with `n_out` interpolated outputs
     for a [batch, dim] state and f(y) = y W (+ b) - checkpoints recomputed from y0 into the handle's scratch, one launch."""
+    _create, _destroy = 'mi_ode_discrete_linear_grid_create', 'mi_ode_discrete_linear_grid_destroy'
 
     def __init__(self, batch, dim, has_bias, method, n_steps, n_out, device, dtype):
-        from .solvers import _fill_tableau
-        self.lib = N.load()
-        self.device = torch.device(device)
         self.dtype = dtype
         d = N.DiscreteLinearGridDesc()
         d.dtype, d.dim, d.batch, d.has_bias = N.dtype_code(dtype), int(dim), int(batch), int(bool(has_bias))
         d.n_steps, d.n_out = int(n_steps), int(n_out)
-        _fill_tableau(d.tableau, TABLEAUS[method], None)
-        self.desc = d
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            N.check(self.lib.mi_ode_discrete_linear_grid_create(C.byref(d), C.byref(h)), 'mi_ode_discrete_linear_grid_create')
-        self.h = h
+        self._open(device, d, method)
         self.batch, self.dim, self.n_steps, self.n_out, self.has_bias = int(batch), int(dim), int(n_steps), int(n_out), bool(has_bias)
-        self.stats = N.Stats()
-
-    def close(self):
-        if getattr(self, 'h', None):
-            self.lib.mi_ode_discrete_linear_grid_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def profile(self):
         """_FusedLinearEngine.profile() plus 'scratch_bytes': the checkpoint scratch the handle owns (grid x n_steps x 16 x D elements)."""
@@ -433,42 +410,19 @@ class _FusedLinearGridEngine(object):
     def sweep(self, W, b, gplan, y0, grad_out):
         """(grad_y0 [batch, dim], grad_W [dim, dim] in W's [in, out] layout, grad_b [dim] or None) from y0 [batch, dim] and the gradient of
         the loss with respect to the n_out outputs [n_out, batch, dim]; gplan: the GridPlan of the call."""
-        r = N.Rhs()
-        r.kind, r.sign, r.hidden = N.RHS_LINEAR, 1.0, 0
-        W = W.contiguous()
-        r.w[0] = W.data_ptr()
-        if b is not None:
-            b = b.contiguous()
-            r.b[0] = b.data_ptr()
+        r, _keep, (g_y0, g_w, g_b) = _linear_io(self, W, b)
         y0, grad_out = y0.contiguous(), grad_out.contiguous()
-        g_y0 = torch.empty(self.batch, self.dim, dtype=self.dtype, device=self.device)
-        g_w = torch.empty(self.dim, self.dim, dtype=self.dtype, device=self.device)
-        g_b = torch.empty(self.dim, dtype=self.dtype, device=self.device) if b is not None else None
         grid = (C.c_double * (self.n_steps + 1))(*[float(v) for v in gplan.grid])
         step = (C.c_int32 * self.n_out)(*[int(v) for v in gplan.out_step])
         w = (C.c_double * self.n_out)(*[float(v) for v in gplan.out_w])
-        with torch.cuda.device(self.device):
-            rc = N.check(self.lib.mi_ode_discrete_linear_grid_sweep(self.h, C.byref(r), grid, step, w, y0.data_ptr(), grad_out.data_ptr(), g_y0.data_ptr(),
-                                                                    g_w.data_ptr(), None if g_b is None else g_b.data_ptr(), C.byref(self.stats),
-                                                                    N.stream_ptr(self.device)), 'mi_ode_discrete_linear_grid_sweep')
-        if rc != 0:
-            from .adjoint import HandoffTimeout
-            if rc & N.ST_SYNC_TIMEOUT:
-                raise HandoffTimeout(N.status_message(rc))
-            raise AssertionError(N.status_message(rc))
-        return g_y0, g_w, g_b
+        return self._run('mi_ode_discrete_linear_grid_sweep', (C.byref(r), grid, step, w, y0.data_ptr(), grad_out.data_ptr(), g_y0.data_ptr(),
+                                                               g_w.data_ptr(), None if g_b is None else g_b.data_ptr()), (g_y0, g_w, g_b))
 
 
 def _cached_linear_grid_engine(*key):
     """_cached_linear_engine for the own-grid kernel: the same cache (and the same rule: eviction only drops the cache's reference), the
     key carries (n_steps, n_out)."""
-    eng = _LINEAR_ENGINES.get(('own grid',) + key)
-    if eng is None:
-        eng = _FusedLinearGridEngine(*key)
-        while len(_LINEAR_ENGINES) >= 4:
-            _LINEAR_ENGINES.pop(next(iter(_LINEAR_ENGINES)))
-        _LINEAR_ENGINES[('own grid',) + key] = eng
-    return eng
+    return _cached(_LINEAR_ENGINES, ('own grid',) + key, lambda: _FusedLinearGridEngine(*key), False)
 
 
 def _on_device(x):
@@ -517,20 +471,51 @@ class _LinearPlan(object):
         return gp
 
 
+def _state_refusal(y0, method, what):
+    """Why `what` does not take a state like y0 under `method`, or ''."""
+    if not isinstance(y0, torch.Tensor):
+        return 'a tuple state (the %s takes one state tensor)' % what
+    if y0.dtype not in (torch.float32, torch.float64):
+        return 'dtype %s (the %s is float32 / float64)' % (str(y0.dtype).replace('torch.', ''), what)
+    if method not in TABLEAUS:
+        return 'method %r' % (method,)
+    return ''
+
+
+def _trace_kind(func, y0, method, accepted):
+    """((trace, family, info), '') of the Python callable `func` on y0 - traced (or found in the trace cache) and classified - else
+    (None, why not).  accepted: what the caller takes, for the refusal of a device descriptor."""
+    from . import lower as L
+    if getattr(func, 'kind', 0) or getattr(func, 'stage_rhs', None) is not None or not callable(func):
+        return None, 'a device right-hand side descriptor, not %s' % accepted
+    try:
+        if isinstance(func, L.CompiledCallable):
+            tr = func._trace_for(y0, method)
+        else:
+            tr, _hit = L._cached_trace(func, y0, None) if L.TRACE_CACHE else (None, False)
+            if tr is None:
+                tr = L.trace(func, y0)
+        rows = 1
+        for s_ in tr.batch_shape:
+            rows *= int(s_)
+        kind, info = L.classify(tr, rows=rows)
+    except L.TraceError as e:
+        return None, 'the callable cannot be lowered: %s' % e
+    except Exception as e:                               # the callable itself failed on the proxies
+        return None, 'tracing failed: %s: %s' % (type(e).__name__, e)
+    return (tr, kind, info), ''
+
+
 def _linear_plan(func, params, method, y0, like=None, n_points=None, own_grid=None):
     """(_LinearPlan, '') when the fused linear sweep takes this call, else (None, why not).  like: the solution (or any tensor of its
     shape [N, ...]); without one, n_points is the number of grid points - or a tuple of them, the distinct segment lengths of an own-grid
     recompute: the plan's engine is the first one's, the others' are created with it.  own_grid: (n_steps, n_out) of a solve on a grid
     of its own - the plan then holds the own-grid kernel's engine (the same conditions, n_steps <= 1024 in place of the limit on the
     points of `t`).  Creates (or finds) every engine - at the call, not in backward."""
-    from . import lower as L
     from . import models as M
-    if not isinstance(y0, torch.Tensor):
-        return None, 'a tuple state (the fused linear sweep takes one state tensor)'
-    if y0.dtype not in (torch.float32, torch.float64):
-        return None, 'dtype %s (the fused linear sweep is float32 / float64)' % str(y0.dtype).replace('torch.', '')
-    if method not in TABLEAUS:
-        return None, 'method %r' % (method,)
+    why = _state_refusal(y0, method, 'fused linear sweep')
+    if why:
+        return None, why
     if y0.dim() < 1:
         return None, 'a 0-d state'
     dim = int(y0.shape[-1])
@@ -539,27 +524,13 @@ def _linear_plan(func, params, method, y0, like=None, n_points=None, own_grid=No
             return None, 'the state\'s last axis is %d, the module\'s dim %d' % (dim, func.dim)
         W, b, how = func.weight, func.bias, 'W'
     else:
-        if getattr(func, 'kind', 0) or getattr(func, 'stage_rhs', None) is not None or not callable(func):
-            return None, 'a device right-hand side descriptor, not a models.LinearODEFunc or a Python callable'
         nfe = getattr(func, 'nfe', None)                 # (tracing runs a module's forward on proxies: not an evaluation the caller counts)
-        try:
-            if isinstance(func, L.CompiledCallable):
-                tr = func._trace_for(y0, method)
-            else:
-                tr, _hit = L._cached_trace(func, y0, None) if L.TRACE_CACHE else (None, False)
-                if tr is None:
-                    tr = L.trace(func, y0)
-            rows = 1
-            for s_ in tr.batch_shape:
-                rows *= int(s_)
-            kind, info = L.classify(tr, rows=rows)
-        except L.TraceError as e:
-            return None, 'the callable cannot be lowered: %s' % e
-        except Exception as e:                           # the callable itself failed on the proxies
-            return None, 'tracing failed: %s: %s' % (type(e).__name__, e)
-        finally:
-            if isinstance(nfe, int) and getattr(func, 'nfe', nfe) != nfe:
-                func.nfe = nfe
+        traced, why = _trace_kind(func, y0, method, 'a models.LinearODEFunc or a Python callable')
+        if isinstance(nfe, int) and getattr(func, 'nfe', nfe) != nfe:
+            func.nfe = nfe
+        if traced is None:
+            return None, why
+        tr, kind, info = traced
         if kind != 'linear':
             return None, 'the callable lowers to the %r family, not to y @ W (+ b)' % kind
         how, widx = info['W']
@@ -627,29 +598,13 @@ def _row_plan(func, params, method, y0, build=True):
     """(_RowPlan, '') when the fused row-local sweep takes this call, else (None, why not).  Traces, classifies, generates the vjp and
     builds the plugin - at the call, not in backward."""
     from . import lower as L
-    if not isinstance(y0, torch.Tensor):
-        return None, 'a tuple state (the fused row-local sweep takes one state tensor)'
-    if y0.dtype not in (torch.float32, torch.float64):
-        return None, 'dtype %s (the fused row-local sweep is float32 / float64)' % str(y0.dtype).replace('torch.', '')
-    if method not in TABLEAUS:
-        return None, 'method %r' % (method,)
-    if getattr(func, 'kind', 0) or getattr(func, 'stage_rhs', None) is not None or not callable(func):
-        return None, 'a device right-hand side descriptor, not a Python callable'
-    try:
-        if isinstance(func, L.CompiledCallable):
-            tr = func._trace_for(y0, method)
-        else:
-            tr, _hit = L._cached_trace(func, y0, None) if L.TRACE_CACHE else (None, False)
-            if tr is None:
-                tr = L.trace(func, y0)
-        rows = 1
-        for s_ in tr.batch_shape:
-            rows *= int(s_)
-        kind, _info = L.classify(tr, rows=rows)
-    except L.TraceError as e:
-        return None, 'the callable cannot be lowered: %s' % e
-    except Exception as e:                               # the callable itself failed on the proxies
-        return None, 'tracing failed: %s: %s' % (type(e).__name__, e)
+    why = _state_refusal(y0, method, 'fused row-local sweep')
+    if why:
+        return None, why
+    traced, why = _trace_kind(func, y0, method, 'a Python callable')     # (func.nfe is left as the trace moved it - _linear_plan restores it)
+    if traced is None:
+        return None, why
+    tr, kind, _info = traced
     if kind != 'rowlocal':
         return None, 'the callable lowers to the %r family, which has no generated vjp (row-local programs do)' % kind
     plist, n_params = L.vjp_params(tr)
@@ -897,7 +852,7 @@ class _OdeintDiscrete(torch.autograd.Function):
             ans = (ans,)
         ctx.t = t
         step_size = (options or {}).get('step_size')
-        gplan = getattr(ctx, 'grid_plan', None)          # (_OdeintDiscreteLinearGrid has formed it for its planning)
+        gplan = getattr(ctx, 'grid_plan', None)          # (_OdeintDiscretePlanned has formed it for its planning)
         ctx.grid_plan = _grid_plan(t, step_size, ans[0].dtype) if gplan is None and step_size is not None else gplan
         if ctx.grid_plan is None:
             ctx.save_for_backward(*ans)
@@ -920,57 +875,22 @@ class _OdeintDiscrete(torch.autograd.Function):
         return (None,) * 7 + tuple(gp) + tuple(g_y0)
 
 
-class _OdeintDiscreteLowered(torch.autograd.Function):
-    """_OdeintDiscrete with the outcome of the row-local planning - (plan, '') or (None, why not) - in front of its arguments."""
+_Plans = collections.namedtuple('_Plans', 'mlp64 grid_plan linear_grid_plan linear_plan row_plan')
+
+
+class _OdeintDiscretePlanned(torch.autograd.Function):
+    """_OdeintDiscrete with what the call planned in front of its arguments: the call's `mlp64`, its GridPlan (None on the default grid)
+    and the outcomes - (plan, '') or (None, why not); None where the route is off - of the own-grid kernel's, the linear and the
+    row-local planning.  _stored_sweep and _own_grid_sweep read them from ctx."""
 
     @staticmethod
-    def forward(ctx, row_plan, *args):
-        ctx.row_plan = row_plan
+    def forward(ctx, plans, *args):
+        ctx.mlp64, ctx.grid_plan, ctx.linear_grid_plan, ctx.linear_plan, ctx.row_plan = plans
         return _OdeintDiscrete.forward(ctx, *args)
 
     @staticmethod
     def backward(ctx, *grad_output):
         return (None,) + _OdeintDiscrete.backward(ctx, *grad_output)
-
-
-class _OdeintDiscreteLinear(torch.autograd.Function):
-    """_OdeintDiscrete with the outcomes of the linear and the row-local planning (the latter None when `lower` is off) in front of its arguments."""
-
-    @staticmethod
-    def forward(ctx, linear_plan, row_plan, *args):
-        ctx.linear_plan, ctx.row_plan = linear_plan, row_plan
-        return _OdeintDiscrete.forward(ctx, *args)
-
-    @staticmethod
-    def backward(ctx, *grad_output):
-        return (None, None) + _OdeintDiscrete.backward(ctx, *grad_output)
-
-
-class _OdeintDiscreteLinearGrid(torch.autograd.Function):
-    """_OdeintDiscreteLinear with the call's GridPlan and the outcome of the own-grid kernel's planning in front of its arguments."""
-
-    @staticmethod
-    def forward(ctx, grid_plan, linear_grid_plan, linear_plan, row_plan, *args):
-        ctx.grid_plan, ctx.linear_grid_plan, ctx.linear_plan, ctx.row_plan = grid_plan, linear_grid_plan, linear_plan, row_plan
-        return _OdeintDiscrete.forward(ctx, *args)
-
-    @staticmethod
-    def backward(ctx, *grad_output):
-        return (None, None, None, None) + _OdeintDiscrete.backward(ctx, *grad_output)
-
-
-class _OdeintDiscreteMlp64(torch.autograd.Function):
-    """_OdeintDiscreteLinearGrid (each plan None where its route is off) with the call's `mlp64` in front of its arguments."""
-
-    @staticmethod
-    def forward(ctx, mlp64, grid_plan, linear_grid_plan, linear_plan, row_plan, *args):
-        ctx.mlp64 = mlp64
-        ctx.grid_plan, ctx.linear_grid_plan, ctx.linear_plan, ctx.row_plan = grid_plan, linear_grid_plan, linear_plan, row_plan
-        return _OdeintDiscrete.forward(ctx, *args)
-
-    @staticmethod
-    def backward(ctx, *grad_output):
-        return (None, None, None, None, None) + _OdeintDiscrete.backward(ctx, *grad_output)
 
 
 def _mlp64_check(mlp64, func, params, method, tensor_input, ys, n_points):
@@ -1040,75 +960,39 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=
     params = _params_of(func, y0, t) if torch.is_grad_enabled() else ()
     # (_forward_func: models.ODEBlock hands the forward solve the network's own fused descriptor, as its inference branch does)
     fwd = func if _forward_func is None else _forward_func
+    rest = (func, fwd, method, options, t, tensor_input, len(params)) + tuple(params) + tuple(ys)
+    if linear is False and lower is False and mlp64 is False:
+        out = _OdeintDiscrete.apply(*rest)
+        return out[0] if tensor_input else tuple(out)
+    # One planning pass, at the call.  n_sweep: the points of the stored trajectories the backward sweeps - `t` itself, or on a grid of
+    # its own the distinct lengths of the segments of the recompute (the first segment's first).
+    grad = torch.is_grad_enabled()
+    off = (None, 'gradients are disabled')
     step_size = (options or {}).get('step_size')
-    if linear is not False and step_size is not None:
-        # a grid of its own: the kernel that recomputes its checkpoints, else the default-grid sweep over a recompute (planned for the
-        # segment length the backward will use)
-        dtype = y0.dtype if tensor_input else ys[0].dtype
-        gplan = _grid_plan(t, step_size, dtype)
+    gplan, n_sweep = None, (t.numel(),)
+    if step_size is not None:
+        gplan = _grid_plan(t, step_size, ys[0].dtype)
         n_grid_steps = int(gplan.grid.shape[0]) - 1
-        off = (None, 'gradients are disabled')
-        kern_plan = off if not torch.is_grad_enabled() else (None, 'discrete.GRID_KERNEL is False') if not GRID_KERNEL else \
-            _linear_plan(func, params, method, y0, own_grid=(n_grid_steps, len(gplan.out_step)))
-        lin_plan = (None, '')
-        if kern_plan[0] is None:
-            seg = _segments(n_grid_steps, sum(y_.numel() * y_.element_size() for y_ in ys))
-            lin_plan = off if not torch.is_grad_enabled() else _linear_plan(func, params, method, y0, n_points=_segment_points(seg))
+        n_sweep = _segment_points(_segments(n_grid_steps, sum(y_.numel() * y_.element_size() for y_ in ys)))
+    kern_plan = lin_plan = row_plan = None
+
+    def taken():
+        return any(p is not None and p[0] is not None for p in (kern_plan, lin_plan, row_plan))
+    if linear is not False:
+        if gplan is not None:                            # the kernel that recomputes its checkpoints
+            kern_plan = off if not grad else (None, 'discrete.GRID_KERNEL is False') if not GRID_KERNEL else \
+                _linear_plan(func, params, method, y0, own_grid=(n_grid_steps, len(gplan.out_step)))
+        if not taken():                                  # the default-grid sweep, over the recompute where the grid is the call's own
+            lin_plan = off if not grad else _linear_plan(func, params, method, y0, n_points=n_sweep)
             if linear is True and lin_plan[0] is None:
                 raise ValueError('odeint_discrete(linear=True): the fused linear sweep does not take this call: ' + lin_plan[1])
-        row_plan = None
-        if lower is not False and kern_plan[0] is None and lin_plan[0] is None:
-            row_plan = _row_plan(func, params, method, y0) if torch.is_grad_enabled() else (None, 'gradients are disabled')
-            if lower is True and row_plan[0] is None:
-                raise ValueError('odeint_discrete(lower=True): the fused row-local sweep does not take this call: ' + row_plan[1])
-        rest = (func, fwd, method, options, t, tensor_input, len(params)) + tuple(params) + tuple(ys)
-        if mlp64 is not False:
-            if kern_plan[0] is None and lin_plan[0] is None and (row_plan is None or row_plan[0] is None):
-                _mlp64_check(mlp64, func, params, method, tensor_input, ys, seg[1] - seg[0] + 1)
-            out = _OdeintDiscreteMlp64.apply(mlp64, gplan, kern_plan, lin_plan, row_plan, *rest)
-        else:
-            out = _OdeintDiscreteLinearGrid.apply(gplan, kern_plan, lin_plan, row_plan, *rest)
-        return out[0] if tensor_input else tuple(out)
-    if linear is not False:
-        lin_plan = _linear_plan(func, params, method, y0, n_points=t.numel()) if torch.is_grad_enabled() else (None, 'gradients are disabled')
-        if linear is True and lin_plan[0] is None:
-            raise ValueError('odeint_discrete(linear=True): the fused linear sweep does not take this call: ' + lin_plan[1])
-        row_plan = None
-        if lower is not False and lin_plan[0] is None:
-            row_plan = _row_plan(func, params, method, y0) if torch.is_grad_enabled() else (None, 'gradients are disabled')
-            if lower is True and row_plan[0] is None:
-                raise ValueError('odeint_discrete(lower=True): the fused row-local sweep does not take this call: ' + row_plan[1])
-        rest = (func, fwd, method, options, t, tensor_input, len(params)) + tuple(params) + tuple(ys)
-        if mlp64 is not False:
-            if lin_plan[0] is None and (row_plan is None or row_plan[0] is None):
-                _mlp64_check(mlp64, func, params, method, tensor_input, ys, t.numel())
-            out = _OdeintDiscreteMlp64.apply(mlp64, None, None, lin_plan, row_plan, *rest)
-        else:
-            out = _OdeintDiscreteLinear.apply(lin_plan, row_plan, *rest)
-        return out[0] if tensor_input else tuple(out)
-    if lower is not False:
-        row_plan = _row_plan(func, params, method, y0) if torch.is_grad_enabled() else (None, 'gradients are disabled')
+    if lower is not False and not taken():
+        row_plan = _row_plan(func, params, method, y0) if grad else off
         if lower is True and row_plan[0] is None:
             raise ValueError('odeint_discrete(lower=True): the fused row-local sweep does not take this call: ' + row_plan[1])
-        rest = (func, fwd, method, options, t, tensor_input, len(params)) + tuple(params) + tuple(ys)
-        if mlp64 is not False:
-            if row_plan[0] is None:
-                _mlp64_check(mlp64, func, params, method, tensor_input, ys, t.numel())
-            out = _OdeintDiscreteMlp64.apply(mlp64, None, None, None, row_plan, *rest)
-        else:
-            out = _OdeintDiscreteLowered.apply(row_plan, *rest)
-        return out[0] if tensor_input else tuple(out)
-    rest = (func, fwd, method, options, t, tensor_input, len(params)) + tuple(params) + tuple(ys)
-    if mlp64 is not False:
-        n_pts = t.numel()
-        if step_size is not None:                        # a grid of its own: the backward sweeps the recomputed grid in segments
-            n_grid = int(_grid_plan(t, step_size, ys[0].dtype).grid.shape[0]) - 1
-            seg = _segments(n_grid, sum(y_.numel() * y_.element_size() for y_ in ys))
-            n_pts = seg[1] - seg[0] + 1
-        _mlp64_check(mlp64, func, params, method, tensor_input, ys, n_pts)
-        out = _OdeintDiscreteMlp64.apply(mlp64, None, None, None, None, *rest)
-    else:
-        out = _OdeintDiscrete.apply(*rest)
+    if mlp64 is not False and not taken():
+        _mlp64_check(mlp64, func, params, method, tensor_input, ys, n_sweep[0])
+    out = _OdeintDiscretePlanned.apply(_Plans(mlp64, gplan, kern_plan, lin_plan, row_plan), *rest)
     return out[0] if tensor_input else tuple(out)
 
 
