@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from tfdiffeq_amd import _native as N
+from tfdiffeq_amd import adjoint as A
 from tfdiffeq_amd import discrete as D
 from tfdiffeq_amd import models, odeint_discrete
 
@@ -154,19 +155,24 @@ def test_the_float64_check_plans_for_the_segment_the_backward_sweeps_on_a_grid_o
 
 
 _MLP_KEY = lambda n: (33, 3, 5, 'rk4', n, 'cuda:0', 0, True)                                  # noqa: E731
-CACHES = {
-    '_cached_engine': ('_FusedDiscreteEngine', '_ENGINES', _MLP_KEY, True),
-    '_cached_engine64': ('_FusedDiscreteEngine64', '_ENGINES64', _MLP_KEY, True),
-    '_cached_linear_engine': ('_FusedLinearEngine', '_LINEAR_ENGINES', lambda n: (17, 6, True, 'heun', n, 'cuda:0', torch.float64), False),
-    '_cached_linear_grid_engine': ('_FusedLinearGridEngine', '_LINEAR_ENGINES', lambda n: (17, 6, True, 'heun', n, 3, 'cuda:0', torch.float64), False),
+_ADJ_KEY = lambda n: (33, 3, 5, 1e-6, 1e-8, 0.9, 10.0, 0.2, n, 'cuda:0', True)                   # noqa: E731
+CACHES = {                                                   # name: (module, engine class, cache, key of n, close_on_evict)
+    '_cached_engine': (D, '_FusedDiscreteEngine', '_ENGINES', _MLP_KEY, True),
+    '_cached_engine64': (D, '_FusedDiscreteEngine64', '_ENGINES64', _MLP_KEY, True),
+    '_cached_linear_engine': (D, '_FusedLinearEngine', '_LINEAR_ENGINES', lambda n: (17, 6, True, 'heun', n, 'cuda:0', torch.float64), False),
+    '_cached_linear_grid_engine': (D, '_FusedLinearGridEngine', '_LINEAR_ENGINES', lambda n: (17, 6, True, 'heun', n, 3, 'cuda:0', torch.float64),
+                                   False),
+    '_cached_adjoint_engine': (A, '_FusedAdjointEngine', '_ENGINES', _ADJ_KEY, True),
+    '_cached_linear_adjoint_engine': (A, '_LinearAdjointEngine', '_LIN_ENGINES',
+                                      lambda n: (17, 6, torch.float64, 1e-6, 1e-8, 0.9, 10.0, 0.2, n, 'cuda:0'), True),
 }
 
 
 @pytest.mark.parametrize('name', sorted(CACHES))
 def test_the_cache_contract_of_every_engine(monkeypatch, name):
-    """A hit returns the same object; the fifth key evicts the oldest; a create that raises evicts nothing; an evicted MLP engine is
-    closed, an evicted linear engine is only dropped (a pending plan may still hold it)."""
-    engine, cache, key, closes = CACHES[name]
+    """A hit returns the same object; the fifth key evicts the oldest; a create that raises evicts nothing; an evicted MLP or adjoint engine
+    is closed, an evicted linear sweep engine is only dropped (a pending plan may still hold it)."""
+    mod, engine, cache, key, closes = CACHES[name]
 
     class Fake(object):
         made, fail = [], False
@@ -179,21 +185,21 @@ def test_the_cache_contract_of_every_engine(monkeypatch, name):
 
         def close(self):
             self.closed = True
-    monkeypatch.setattr(D, engine, Fake)                     # (the class is looked up when the cache creates)
-    monkeypatch.setattr(D, cache, {})
-    cached = getattr(D, name)
+    monkeypatch.setattr(mod, engine, Fake)                     # (the class is looked up when the cache creates)
+    monkeypatch.setattr(mod, cache, {})
+    cached = getattr(mod, name)
     first = cached(*key(5))
     assert cached(*key(5)) is first and len(Fake.made) == 1 and first.args == key(5)
     for n in (6, 7, 8):
         cached(*key(n))
-    assert len(getattr(D, cache)) == 4 and not first.closed
+    assert len(getattr(mod, cache)) == 4 and not first.closed
     Fake.fail = True
-    before = dict(getattr(D, cache))
+    before = dict(getattr(mod, cache))
     with pytest.raises(N.NativeError):
         cached(*key(9))
-    assert getattr(D, cache) == before and list(getattr(D, cache)) == list(before) and not any(e.closed for e in Fake.made)
+    assert getattr(mod, cache) == before and list(getattr(mod, cache)) == list(before) and not any(e.closed for e in Fake.made)
     Fake.fail = False
     fifth = cached(*key(9))
-    held = list(getattr(D, cache).values())
+    held = list(getattr(mod, cache).values())
     assert len(held) == 4 and first not in held and held[-1] is fifth and held[:3] == Fake.made[1:4]
     assert first.closed is closes and not any(e.closed for e in Fake.made[1:])

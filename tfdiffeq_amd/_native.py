@@ -372,6 +372,17 @@ def status_message(bits):
     return load().mi_ode_status_string(bits).decode('utf-8')
 
 
+def status_text(bits, max_num_steps=None, dt=None):
+    """status_message(bits), in the reference's own words (dopri5.py:85-100) for ST_MAX_STEPS where the caller has a max_num_steps and for
+    ST_DT_UNDERFLOW where it has the step size."""
+    msg = status_message(bits)
+    if bits & ST_MAX_STEPS and max_num_steps is not None:
+        msg = 'max_num_steps exceeded ({}>={})'.format(max_num_steps, max_num_steps)
+    if bits & ST_DT_UNDERFLOW and dt is not None:
+        msg = 'underflow in dt {}'.format(dt)
+    return msg
+
+
 def require_gpu_tensor(x, what='y0'):
     import torch
     if not isinstance(x, torch.Tensor):

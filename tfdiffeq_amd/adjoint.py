@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .engine import HandoffTimeout, _SweepEngine, _cached  # noqa: F401  (HandoffTimeout: callers catch it under this module's name)
 from .odeint import odeint
 
 # The backward solve of the ODEFunc MLP (relu, softplus or tanh) runs as ONE kernel launch per output interval (csrc/mi_ode_adjoint.h) when the
@@ -23,11 +24,7 @@ from .odeint import odeint
 FUSED = os.environ.get('TFDIFFEQ_AMD_FUSED_ADJOINT', '1') != '0'
 FUSED_FORWARD = True          # the forward solve under odeint_adjoint also takes the fused kernels of a network that has them
 _ENGINES = {}
-
-
-class HandoffTimeout(RuntimeError):
-    """The fused adjoint kernel's in-kernel grid hand-off timed out (the GPU is shared with another persistent kernel).  Nothing
-    was committed: the caller may take the generic path.  Every other native failure propagates."""
+_LIN_ENGINES = {}
 
 
 def _flatten(seq):
@@ -63,43 +60,29 @@ class _FlatParams(torch.autograd.Function):
         return (None,) + tuple(out)
 
 
-class _FusedAdjointEngine(object):
+def _open_dopri5(eng, device, d, rtol, atol, safety, ifactor, dfactor, max_num_steps):
+    """The controller fields of an adaptive one-launch descriptor and its handle: dopri5 with the Shampine dense output."""
+    from .dopri5 import _DORMAND_PRINCE_SHAMPINE_TABLEAU, DPS_C_MID
+    d.rtol, d.atol = float(rtol), float(atol)
+    d.safety, d.ifactor, d.dfactor = float(safety), float(ifactor), float(dfactor)
+    d.order, d.init_order = 5, 4                         # dopri5.py:68, 74
+    d.max_num_steps = int(max_num_steps)
+    eng._open(device, d, _DORMAND_PRINCE_SHAMPINE_TABLEAU, DPS_C_MID)
+
+
+class _FusedAdjointEngine(_SweepEngine):
     """Owns one mi_ode_adjoint handle: the augmented system (y, adj_y, adj_t, adj_params) of adjoint.py:57-178 for a
     [batch, dim] float32 state and the dim -> hidden -> hidden -> dim MLP (rhs.MLP: relu, softplus or tanh; time_dependent:
     the first layer sees concat([t, x]), dense_odenet.py:79-84 - adj_params then starts with w_t, the row of W1 that multiplies t)."""
+    _create, _destroy = 'mi_ode_adjoint_create', 'mi_ode_adjoint_destroy'
 
     def __init__(self, batch, dim, hidden, rtol, atol, safety, ifactor, dfactor, max_num_steps, device, time_dependent=False):
-        from .dopri5 import _DORMAND_PRINCE_SHAMPINE_TABLEAU, DPS_C_MID
-        from .solvers import _fill_tableau
-        self.lib = N.load()
-        self.device = torch.device(device)
         d = N.AdjointDesc()
         d.batch, d.dim, d.hidden = int(batch), int(dim), int(hidden)
-        _fill_tableau(d.tableau, _DORMAND_PRINCE_SHAMPINE_TABLEAU, DPS_C_MID)
-        d.rtol, d.atol = float(rtol), float(atol)
-        d.safety, d.ifactor, d.dfactor = float(safety), float(ifactor), float(dfactor)
-        d.order, d.init_order = 5, 4                     # dopri5.py:68, 74
-        d.max_num_steps = int(max_num_steps)
         d.time_dependent = 1 if time_dependent else 0
-        self.desc = d
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            N.check(self.lib.mi_ode_adjoint_create(C.byref(d), C.byref(h)), 'mi_ode_adjoint_create')
-        self.h = h
+        _open_dopri5(self, device, d, rtol, atol, safety, ifactor, dfactor, max_num_steps)
         self.batch, self.dim = int(batch), int(dim)
-        self.n_params = int(self.lib.mi_ode_adjoint_num_params(h))
-        self.stats = N.Stats()
-
-    def close(self):
-        if getattr(self, 'h', None):
-            self.lib.mi_ode_adjoint_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.n_params = int(self.lib.mi_ode_adjoint_num_params(self.h))
 
     def _rhs(self, mlp):
         r = N.Rhs()
@@ -114,22 +97,10 @@ class _FusedAdjointEngine(object):
         a_out = torch.empty_like(adj_y)
         t_out = torch.empty_like(adj_t)
         p_out = torch.empty_like(adj_params)
-        with torch.cuda.device(self.device):
-            rc = N.check(self.lib.mi_ode_adjoint_segment(
-                self.h, C.byref(r), y.data_ptr(), adj_y.data_ptr(), adj_t.data_ptr(), adj_params.data_ptr(), float(t_start), float(t_end),
-                None, a_out.data_ptr(), t_out.data_ptr(), p_out.data_ptr(), C.byref(self.stats), N.stream_ptr(self.device)),
-                'mi_ode_adjoint_segment')
+        out = self._run('mi_ode_adjoint_segment', (C.byref(r), y.data_ptr(), adj_y.data_ptr(), adj_t.data_ptr(), adj_params.data_ptr(), float(t_start),
+                                                   float(t_end), None, a_out.data_ptr(), t_out.data_ptr(), p_out.data_ptr()), (a_out, t_out, p_out))
         del keep
-        if rc != 0:
-            if rc & N.ST_SYNC_TIMEOUT:
-                raise HandoffTimeout(N.status_message(rc))
-            msg = N.status_message(rc)
-            if rc & N.ST_MAX_STEPS:
-                msg = 'max_num_steps exceeded ({}>={})'.format(self.desc.max_num_steps, self.desc.max_num_steps)
-            if rc & N.ST_DT_UNDERFLOW:
-                msg = 'underflow in dt {}'.format(self.stats.dt)
-            raise AssertionError(msg)                      # what the reference's solver raises (dopri5.py:85-100)
-        return a_out, t_out, p_out
+        return out
 
     def dynamics(self, mlp, y, adj_y, t=0.0):
         """One evaluation of the augmented dynamics at time t (adjoint.py:69-105): (f, -adj_y^T df/dy, -adj_y^T df/dparams)."""
@@ -137,20 +108,14 @@ class _FusedAdjointEngine(object):
         y, adj_y = y.contiguous(), adj_y.contiguous()
         f, vy = torch.empty_like(y), torch.empty_like(y)
         vp = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(self.lib.mi_ode_adjoint_dynamics_at(self.h, C.byref(r), float(t), y.data_ptr(), adj_y.data_ptr(), f.data_ptr(), vy.data_ptr(),
-                                                        vp.data_ptr(), N.stream_ptr(self.device)), 'mi_ode_adjoint_dynamics_at')
+        out = self._run('mi_ode_adjoint_dynamics_at', (C.byref(r), float(t), y.data_ptr(), adj_y.data_ptr(), f.data_ptr(), vy.data_ptr(), vp.data_ptr()),
+                        (f, vy, vp), stats=False)
         del keep
-        return f, vy, vp
+        return out
 
 
 def _cached_adjoint_engine(*key):
-    eng = _ENGINES.get(key)
-    if eng is None:
-        while len(_ENGINES) >= 4:
-            _ENGINES.pop(next(iter(_ENGINES))).close()
-        eng = _ENGINES[key] = _FusedAdjointEngine(*key)
-    return eng
+    return _cached(_ENGINES, key, lambda: _FusedAdjointEngine(*key), True)
 
 
 def clear_adjoint_engines():
@@ -160,43 +125,19 @@ def clear_adjoint_engines():
         _LIN_ENGINES.pop(next(iter(_LIN_ENGINES))).close()
 
 
-class _LinearAdjointEngine(object):
+class _LinearAdjointEngine(_SweepEngine):
     """Owns one mi_ode_linadj handle: the augmented system (y, adj_y, adj_t, adj_params) of adjoint.py:57-178 for f = y W + b on a
     [batch, dim] float32 / float64 state, ONE launch per output interval (csrc/mi_ode_linadj.h)."""
+    _create, _destroy = 'mi_ode_linadj_create', 'mi_ode_linadj_destroy'
 
     def __init__(self, batch, dim, dtype, rtol, atol, safety, ifactor, dfactor, max_num_steps, device):
-        from .dopri5 import _DORMAND_PRINCE_SHAMPINE_TABLEAU, DPS_C_MID
-        from .solvers import _fill_tableau
-        self.lib = N.load()
-        self.device = torch.device(device)
         self.dtype = dtype
         d = N.LinAdjDesc()
         d.batch, d.dim, d.dtype = int(batch), int(dim), N.dtype_code(dtype)
-        _fill_tableau(d.tableau, _DORMAND_PRINCE_SHAMPINE_TABLEAU, DPS_C_MID)
-        d.rtol, d.atol = float(rtol), float(atol)
-        d.safety, d.ifactor, d.dfactor = float(safety), float(ifactor), float(dfactor)
-        d.order, d.init_order = 5, 4                     # dopri5.py:68, 74
-        d.max_num_steps = int(max_num_steps)
-        self.desc = d
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            N.check(self.lib.mi_ode_linadj_create(C.byref(d), C.byref(h)), 'mi_ode_linadj_create')
-        self.h = h
+        _open_dopri5(self, device, d, rtol, atol, safety, ifactor, dfactor, max_num_steps)
         self.batch, self.dim = int(batch), int(dim)
-        self.stats = N.Stats()
         self._scalars = (C.c_double * 2)()
         self.scalars = (0.0, 0.0)
-
-    def close(self):
-        if getattr(self, 'h', None):
-            self.lib.mi_ode_linadj_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def segment(self, W, b, y, adj_y, adj_t, adj_params, t_start, t_end, grad_out=None):
         """odeint(augmented_dynamics, (y, adj_y, adj_t, adj_params), [t_start, t_end])[..][1] (adjoint.py:148-160) without the y
@@ -209,22 +150,13 @@ class _LinearAdjointEngine(object):
         p_out = torch.empty_like(adj_params)
         if grad_out is not None:
             grad_out = grad_out.contiguous()
-        with torch.cuda.device(self.device):
-            rc = N.check(self.lib.mi_ode_linadj_segment(
-                self.h, W.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), adj_y.data_ptr(), adj_t.data_ptr(),
-                adj_params.data_ptr(), grad_out.data_ptr() if grad_out is not None else None, float(t_start), float(t_end), a_out.data_ptr(),
-                t_out.data_ptr(), p_out.data_ptr(), None, self._scalars, C.byref(self.stats), N.stream_ptr(self.device)), 'mi_ode_linadj_segment')
-        self.scalars = (float(self._scalars[0]), float(self._scalars[1]))
-        if rc != 0:
-            if rc & N.ST_SYNC_TIMEOUT:
-                raise HandoffTimeout(N.status_message(rc))
-            msg = N.status_message(rc)
-            if rc & N.ST_MAX_STEPS:
-                msg = 'max_num_steps exceeded ({}>={})'.format(self.desc.max_num_steps, self.desc.max_num_steps)
-            if rc & N.ST_DT_UNDERFLOW:
-                msg = 'underflow in dt {}'.format(self.stats.dt)
-            raise AssertionError(msg)                      # what the reference's solver raises (dopri5.py:85-100)
-        return a_out, t_out, p_out
+        try:
+            return self._run('mi_ode_linadj_segment', (
+                W.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), adj_y.data_ptr(), adj_t.data_ptr(), adj_params.data_ptr(),
+                grad_out.data_ptr() if grad_out is not None else None, float(t_start), float(t_end), a_out.data_ptr(), t_out.data_ptr(),
+                p_out.data_ptr(), None, self._scalars), (a_out, t_out, p_out))
+        finally:                                         # (a failed segment leaves its scalars too, as the status does)
+            self.scalars = (float(self._scalars[0]), float(self._scalars[1]))
 
     def profile(self):
         out = (C.c_double * 8)()
@@ -234,17 +166,8 @@ class _LinearAdjointEngine(object):
         return dict(zip(keys, list(out)))
 
 
-_LIN_ENGINES = {}
-
-
 def _cached_linear_adjoint_engine(*key):
-    eng = _LIN_ENGINES.get(key)
-    if eng is None:
-        eng = _LinearAdjointEngine(*key)                 # (evict only after a successful create: a refusal must not cost live engines)
-        while len(_LIN_ENGINES) >= 4:
-            _LIN_ENGINES.pop(next(iter(_LIN_ENGINES))).close()
-        _LIN_ENGINES[key] = eng
-    return eng
+    return _cached(_LIN_ENGINES, key, lambda: _LinearAdjointEngine(*key), True)
 
 
 def canonical_to_module_order(base, theta):

@@ -411,15 +411,10 @@ static void multistep_rhs(const mi_ode_solver* h, RhsParams& r) {
 }
 
 static void fill_step_args(mi_ode_solver* h, StepArgs& A) {
-  const mi_ode_tableau& tb = h->d.tableau;
   memset(&A, 0, sizeof(A));
   A.ctl = h->ctl; A.planes = h->planes; A.stride = h->stride; A.batch = h->d.batch; A.dim = (int)h->d.dim;
   A.interp = h->d.interp; A.out = h->cur_out; A.t_out = h->t_out_dev; A.n_plane = h->n;
-  for (int i = 0; i < h->S; ++i) {
-    A.alpha[i] = tb.alpha[i];
-    for (int j = 0; j <= i; ++j) A.beta[i][j] = tb.beta[i][j];
-  }
-  for (int j = 0; j <= h->S; ++j) { A.e[j] = tb.c_error[j]; A.cmid[j] = tb.c_mid[j]; A.csol[j] = tb.c_sol[j]; }
+  fill_tableau(A, h->d.tableau, h->S);
   A.partials = h->partials; A.rhs = h->rhs;
   A.ticket = h->fused_ctl ? h->ticket : nullptr;
   A.cp = h->cp;
@@ -502,10 +497,8 @@ extern "C" int mi_ode_create(const mi_ode_desc* desc, mi_ode_handle* out) {
   }
   h->num_cus = prop.multiProcessorCount;
   // RHS parameters
-  memcpy(h->rhs.s, desc->rhs.scalars, sizeof(h->rhs.s));
-  for (int i = 0; i < 3; ++i) { h->rhs.w[i] = desc->rhs.w[i]; h->rhs.b[i] = desc->rhs.b[i]; }
+  fill_rhs(h->rhs, desc->rhs);
   h->rhs.sign = desc->rhs.sign == 0.0 ? 1.0 : desc->rhs.sign;
-  h->rhs.hidden = desc->rhs.hidden;
   int rc = pick_family(h);
   if (rc != 0) { mi_ode_destroy(h); return rc; }
   if (h->family == FAM_LINEAR_MFMA && h->lin_dp == 256) {   // streamed W: the copy in consumption order (256 x 256 elements, refreshed before every launch)

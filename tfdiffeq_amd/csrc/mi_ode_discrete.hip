@@ -79,9 +79,9 @@ extern "C" int mi_ode_discrete_create_td(const mi_ode_discrete_desc* desc, int32
   h->Ppad = (h->P + 63) / 64 * 64;
   h->ntiles = (desc->batch + 31) / 32;
   int cus = 0;
-  rc = disc_device(c, h->fn, 3, &cus, kWhat);
+  rc = handoff_device(h->fn, 3, c.block, c.lds, &cus, kWhat);
   if (rc != 0) { mi_ode_discrete_destroy(h); return rc; }
-  c.grid = disc_cap_grid(h->ntiles, cus);
+  c.grid = handoff_cap_grid(h->ntiles, cus);
   h->SL = (h->P + c.grid - 1) / c.grid;
   const long long per_wg = (h->ntiles + c.grid - 1) / c.grid;
   const size_t slot_floats = (size_t)32 * (2 * (size_t)h->dp + 4 * (size_t)h->hp);
@@ -127,9 +127,7 @@ extern "C" int mi_ode_discrete_sweep(mi_ode_discrete_handle h, const mi_ode_rhs*
   StepArgs& S = A.p.s;
   const mi_ode_tableau& tb = h->d.tableau;
   disc_fill_persist(A.p, c, h->d.batch, h->d.dim);
-  for (int i = 0; i < 8; ++i) S.rhs.s[i] = rhs->scalars[i];
-  for (int i = 0; i < 3; ++i) { S.rhs.w[i] = rhs->w[i]; S.rhs.b[i] = rhs->b[i]; }
-  S.rhs.hidden = rhs->hidden;
+  fill_rhs(S.rhs, *rhs);
   A.act = h->act; A.wpart = h->wpart;
   A.P = h->P; A.Ppad = h->Ppad; A.SL = h->SL; A.td = h->td;
   D.ys = (const float*)ys_dev; D.gys = (const float*)grad_ys_dev; D.lam = (float*)grad_y0_out_dev; D.th_out = (float*)grad_theta_out_dev;

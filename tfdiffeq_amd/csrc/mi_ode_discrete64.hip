@@ -86,9 +86,9 @@ extern "C" int mi_ode_discrete64_create(const mi_ode_discrete_desc* desc, int32_
   h->P = h->td * hd + d * hd + hd + hd * hd + hd + hd * d + d;
   h->ntiles = (desc->batch + 31) / 32;
   int cus = 0;
-  rc = disc_device(c, h->fn, 3, &cus, kWhat);
+  rc = handoff_device(h->fn, 3, c.block, c.lds, &cus, kWhat);
   if (rc != 0) { mi_ode_discrete64_destroy(h); return rc; }
-  c.grid = disc_cap_grid(h->ntiles, cus);
+  c.grid = handoff_cap_grid(h->ntiles, cus);
   h->SL = (h->P + c.grid - 1) / c.grid;
   const long long per_wg = (h->ntiles + c.grid - 1) / c.grid;
   const size_t slot_doubles = (size_t)32 * (2 * (size_t)h->dp + 4 * (size_t)h->hp);
@@ -135,9 +135,7 @@ extern "C" int mi_ode_discrete64_sweep(mi_ode_discrete64_handle h, const mi_ode_
   StepArgs& S = D.p.s;
   const mi_ode_tableau& tb = h->d.tableau;
   disc_fill_persist(D.p, c, h->d.batch, h->d.dim);
-  for (int i = 0; i < 8; ++i) S.rhs.s[i] = rhs->scalars[i];
-  for (int i = 0; i < 3; ++i) { S.rhs.w[i] = rhs->w[i]; S.rhs.b[i] = rhs->b[i]; }
-  S.rhs.hidden = rhs->hidden;
+  fill_rhs(S.rhs, *rhs);
   D.ys = (const double*)ys_dev; D.gys = (const double*)grad_ys_dev; D.lam = (double*)grad_y0_out_dev; D.th_out = (double*)grad_theta_out_dev;
   D.pack = h->pack; D.pack_t = h->pack_t; D.act = h->act; D.wpart = h->wpart;
   D.res = c.res;

@@ -1,28 +1,23 @@
 // Host-only plumbing shared by the one-launch discrete sweeps whose argument block travels through device memory: mi_ode_discrete.hip,
-// mi_ode_discrete64.hip, mi_ode_discrete_linear.hip and mi_ode_discrete_linear_grid.hip.  `what` is the engine's name in front of every
-// error message.  Each sweep is disc_begin, the fill of its argument block, disc_run: hipStreamSynchronize, hipMemcpyAsync, (float64: the
-// two pack launches,) hipLaunchKernel, hipStreamSynchronize.
+// mi_ode_discrete64.hip, mi_ode_discrete_linear.hip and mi_ode_discrete_linear_grid.hip.  Device check, grid cap, hand-off records and
+// spin bounds are those of every hand-off engine (mi_ode_handoff_host.h); what is here is the sweeps' own.  `what` is the engine's name in
+// front of every error message.  Each sweep is disc_begin, the fill of its argument block, disc_run: hipStreamSynchronize, hipMemcpyAsync,
+// (float64: the two pack launches,) hipLaunchKernel, hipStreamSynchronize.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
-#include "mi_ode_host.h"
+#include "mi_ode_handoff_host.h"
 #include "mi_ode_discrete.h"
 
 namespace mi {
 
-struct DiscHost {              // embedded in each handle
+struct DiscHost : HandoffHost {   // embedded in each handle
   int S;                       // stages
-  int grid, block;
-  size_t lds;
-  double* partials;            // hand-off records (2 parities)
   DiscResult* res;             // pinned host
   void* args_host;             // pinned staging of the kernel's argument block ...
   void* args_dev;              // ... and its device copy (the kernel and its non-inlined passes read it with scalar loads)
   size_t args_bytes;
-  unsigned seq;
-  int spin_limit, spin_first;
   double prof_us[3];
 };
 
@@ -39,54 +34,23 @@ inline int disc_check_points(int n_points, const char* what) {
   return MI_ODE_E_INVALID;
 }
 
-// A device, its CU count to *cus, the dynamic LDS attribute on every kernel of fns, the occupancy of the first (c.block, c.lds are set).
-inline int disc_device(const DiscHost& c, const void* const* fns, int n_fns, int* cus, const char* what) {
-  int ndev = 0, dev = 0, per_cu = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); mi_set_error("no HIP device"); return MI_ODE_E_NODEVICE; }
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) { mi_set_error("%s: %s", what, hipGetErrorString(e)); (void)hipGetLastError(); return MI_ODE_E_HIP; }
-  for (int i = 0; i < n_fns; ++i)
-    if (hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds) != hipSuccess) (void)hipGetLastError();
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fns[0], c.block, c.lds) != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    mi_set_error("%s kernel does not fit a compute unit (LDS %zu bytes, %d threads)", what, c.lds, c.block);
-    return MI_ODE_E_HIP;
-  }
-  return 0;
-}
-
-// every workgroup co-resident (the hand-offs spin): at most one per CU
-inline int disc_cap_grid(long long g, int cus) {
-  if (g > cus) g = cus;
-  if (g > kPersistMaxGrid) g = kPersistMaxGrid;
-  return (int)g;
-}
-
 // The grid of the linear sweeps' 16-row tiles of width D: a workgroup per tile, and at least one per 1024 entries of the final fold - a small
 // batch still spreads the fold of D * D + D entries; the extra workgroups own no tile and contribute zeros.
 inline int disc_linear_grid(long long batch, int D, int cus) {
   const long long ntiles = (batch + 15) / 16, fold = ((long long)D * D + D + 1023) / 1024;
-  return disc_cap_grid(ntiles < fold ? fold : ntiles, cus);
+  return handoff_cap_grid(ntiles < fold ? fold : ntiles, cus);
 }
 
 // The common block's memory, after the engine's own allocations (e: their outcome), and the spin bounds.
 inline int disc_alloc(DiscHost& c, hipError_t e, size_t args_bytes, const char* what) {
-  const size_t rec_bytes = (size_t)kMaxBlocks * kRec * sizeof(double);
   c.args_bytes = args_bytes;
-  if (e == hipSuccess) e = hipMalloc((void**)&c.partials, rec_bytes);
+  e = handoff_alloc(c, e, 1 << 22);              // the final hand-off absorbs the skew of a whole sweep (tiles are dealt round-robin: at most one
+                                                 // tile of every step); the first comes right after the weights or slices are staged
   if (e == hipSuccess) e = hipHostMalloc((void**)&c.res, sizeof(DiscResult), hipHostMallocDefault);
   if (e == hipSuccess) e = hipHostMalloc(&c.args_host, args_bytes, hipHostMallocDefault);
   if (e == hipSuccess) e = hipMalloc(&c.args_dev, args_bytes);
-  if (e == hipSuccess) e = hipMemset(c.partials, 0, rec_bytes);
   if (e != hipSuccess) { mi_set_error("%s workspace: %s", what, hipGetErrorString(e)); (void)hipGetLastError(); return MI_ODE_E_HIP; }
   memset(c.res, 0, sizeof(DiscResult));
-  c.seq = 0;
-  c.spin_limit = 1 << 22;                        // the final hand-off absorbs the skew of a whole sweep (tiles are dealt round-robin: at most one
-                                                 // tile of every step): a bound, not a time-out to hit
-  c.spin_first = 1 << 14;                        // residency check (the first hand-off comes right after the weights or slices are staged)
-  if (const char* e3 = getenv("MI_ODE_PERSIST_SPIN_FIRST")) c.spin_first = atoi(e3);
-  if (const char* e2 = getenv("MI_ODE_PERSIST_SPIN_LIMIT")) c.spin_limit = atoi(e2);
   return 0;
 }
 
@@ -108,14 +72,9 @@ inline int disc_begin(DiscHost& c, hipStream_t st) {
 inline void disc_fill_persist(PersistArgs& p, const DiscHost& c, long long batch, int dim) {
   StepArgs& s = p.s;
   s.batch = batch; s.dim = dim; s.n_plane = batch * (long long)dim;
-  s.partials = c.partials;
   s.rhs.sign = 1.0;
   s.cp.n_local = s.n_plane;
-  p.world = 1;
-  p.seq_base = c.seq;
-  p.spin_limit = c.spin_limit;
-  p.spin_first = c.spin_first < c.spin_limit ? c.spin_first : c.spin_limit;
-  p.sleep_first = c.grid <= 32 ? 16 : 32; p.sleep_poll = 2;
+  handoff_fill(p, c);
 }
 
 // a_ij and b_i into the block's ha / hb, in T
@@ -159,8 +118,7 @@ inline int disc_run(DiscHost& c, const void* fn, hipStream_t st, const char* wha
   if (e != hipSuccess) { mi_set_error("%s kernel launch failed: %s", what, hipGetErrorString(e)); (void)hipGetLastError(); return MI_ODE_E_HIP; }
   MI_HIP(hipStreamSynchronize(st));
   *r = *c.res;
-  c.seq += (unsigned)r->handoffs + 16u;
-  if (c.seq >= 0xE0000000u) c.seq = 0;
+  handoff_advance(c, (unsigned)r->handoffs + 16u);
   for (int i = 0; i < 3; ++i) c.prof_us[i] = 0.01 * (double)r->prof[i];
   return 0;
 }

@@ -63,7 +63,7 @@ extern "C" int mi_ode_discrete_linear_create(const mi_ode_discrete_linear_desc* 
   h->esz = desc->dtype == MI_ODE_F64 ? 8 : 4;
   h->fn = desc->dtype == MI_ODE_F64 ? dl_fn<double>(h->D, &c.lds) : dl_fn<float>(h->D, &c.lds);
   int cus = 0;
-  rc = disc_device(c, &h->fn, 1, &cus, kWhat);
+  rc = handoff_device(&h->fn, 1, c.block, c.lds, &cus, kWhat);
   if (rc != 0) { mi_ode_discrete_linear_destroy(h); return rc; }
   c.grid = disc_linear_grid(desc->batch, h->D, cus);
   hipError_t e = hipMalloc((void**)&h->gpart, (size_t)c.grid * ((size_t)h->D * h->D + h->D) * h->esz);

@@ -99,7 +99,7 @@ extern "C" int mi_ode_discrete_linear_grid_create(const mi_ode_discrete_linear_g
   h->esz = desc->dtype == MI_ODE_F64 ? 8 : 4;
   h->fn = desc->dtype == MI_ODE_F64 ? dlg_fn<double>(h->D, &c.lds) : dlg_fn<float>(h->D, &c.lds);
   int cus = 0;
-  rc = disc_device(c, &h->fn, 1, &cus, kWhat);
+  rc = handoff_device(&h->fn, 1, c.block, c.lds, &cus, kWhat);
   if (rc != 0) { mi_ode_discrete_linear_grid_destroy(h); return rc; }
   c.grid = disc_linear_grid(desc->batch, h->D, cus);
   h->scratch_bytes = (size_t)c.grid * (size_t)desc->n_steps * 16u * (size_t)h->D * h->esz;

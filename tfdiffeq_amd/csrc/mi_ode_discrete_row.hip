@@ -55,10 +55,8 @@ extern "C" int mi_ode_discrete_row_sweep(const mi_ode_discrete_row_desc* desc, c
     for (int j = 0; j < i; ++j) A.tb.a[i][j] = tb.beta[i - 1][j];
   }
   for (int i = 0; i < S; ++i) A.tb.b[i] = tb.c_sol[i];
-  memcpy(A.rhs.s, rhs->scalars, sizeof(A.rhs.s));
-  for (int i = 0; i < 3; ++i) { A.rhs.w[i] = rhs->w[i]; A.rhs.b[i] = rhs->b[i]; }
+  fill_rhs(A.rhs, *rhs);
   A.rhs.sign = 1.0;
-  A.rhs.hidden = rhs->hidden;
   const int rc = pl->launch_sweep(&A, d.grid, (hipStream_t)stream);
   const hipError_t e = hipGetLastError();
   if (rc != 0 || e != hipSuccess) {

@@ -158,3 +158,36 @@ void mi_set_error(const char* fmt, ...);
       return MI_ODE_E_HIP;                                                               \
     }                                                                                    \
   } while (0)
+
+// ---- descriptor fields into the kernels' parameter blocks (host only) -----------------------------------------------------------------
+namespace mi {
+
+// the first S rows of the tableau into a StepArgs (a template: StepArgs is only declared here)
+template <class Args>
+inline void fill_tableau(Args& A, const mi_ode_tableau& tb, int S) {
+  for (int i = 0; i < S; ++i) {
+    A.alpha[i] = tb.alpha[i];
+    for (int j = 0; j <= i; ++j) A.beta[i][j] = tb.beta[i][j];
+  }
+  for (int j = 0; j <= S; ++j) { A.e[j] = tb.c_error[j]; A.cmid[j] = tb.c_mid[j]; A.csol[j] = tb.c_sol[j]; }
+}
+
+// the controller scalars of a one-launch adaptive descriptor (the reference's controller, first step chosen by the kernel)
+template <class Desc>
+inline void fill_ctrl(CtrlParams& cp, const Desc& d, long long n_local, int is_f32, int n_stages) {
+  cp.rtol = d.rtol; cp.atol = d.atol; cp.safety = d.safety; cp.ifactor = d.ifactor; cp.dfactor = d.dfactor;
+  cp.inv_ifactor = 1.0 / d.ifactor; cp.inv_dfactor = 1.0 / d.dfactor;
+  cp.max_num_steps = d.max_num_steps > 0 ? d.max_num_steps : 2147483647LL;
+  cp.n_local = n_local;
+  cp.order = d.order; cp.init_order = d.init_order;
+  cp.controller = MI_ODE_CTRL_MISC; cp.is_f32 = is_f32; cp.n_stages = n_stages; cp.auto_first_step = 1;
+}
+
+// scalars, weights, biases and hidden of a right-hand-side descriptor; `sign` is the caller's
+inline void fill_rhs(RhsParams& r, const mi_ode_rhs& rhs) {
+  for (int i = 0; i < 8; ++i) r.s[i] = rhs.scalars[i];
+  for (int i = 0; i < 3; ++i) { r.w[i] = rhs.w[i]; r.b[i] = rhs.b[i]; }
+  r.hidden = rhs.hidden;
+}
+
+}  // namespace mi

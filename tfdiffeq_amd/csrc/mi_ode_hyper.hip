@@ -76,10 +76,8 @@ extern "C" int mi_ode_hyper_run(const mi_ode_hyper* desc, void* stream) {
 
   // f
   const mi_ode_rhs& r = d.rhs;
-  memcpy(A.rhs.s, r.scalars, sizeof(A.rhs.s));
-  for (int i = 0; i < 3; ++i) { A.rhs.w[i] = r.w[i]; A.rhs.b[i] = r.b[i]; }
+  fill_rhs(A.rhs, r);
   A.rhs.sign = r.sign == 0.0 ? 1.0 : r.sign;
-  A.rhs.hidden = r.hidden;
   const mi_ode_hyper_plugin* pl = nullptr;
   switch (r.kind) {
     case MI_ODE_RHS_LORENZ:

@@ -5,7 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include "mi_ode_host.h"
+#include "mi_ode_handoff_host.h"
 #include "mi_ode_linadj.h"
 
 using namespace mi;
@@ -15,8 +15,7 @@ struct mi_ode_linadj {
   int dp;                      // tile width of the kernel instantiation (16 / 32 / 64 / 128 >= dim)
   int is_f32;
   size_t elt;
-  int grid, block;
-  size_t lds;
+  HandoffHost c;               // grid, block, LDS bytes, hand-off records, sequence numbers, spin bounds
   const void* fn;
   long long ntiles;
   char* planes;                // 8 state planes
@@ -24,11 +23,8 @@ struct mi_ode_linadj {
   double *pw, *cvec, *g0, *lmat, *mmat, *theta, *ktab;
   void *gpart, *wpad;
   long long* skew;
-  double* partials;            // hand-off records (2 parities)
   Ctl* ctl_dev;
   LinAdjResult* res;           // pinned host
-  unsigned seq;
-  int spin_limit, spin_first, sleep_first, sleep_poll;
   long long n_launches;
 };
 
@@ -75,7 +71,7 @@ extern "C" int mi_ode_linadj_destroy(mi_ode_linadj_handle h) {
   if (h->gpart) (void)hipFree(h->gpart);
   if (h->wpad) (void)hipFree(h->wpad);
   if (h->skew) (void)hipFree(h->skew);
-  if (h->partials) (void)hipFree(h->partials);
+  if (h->c.partials) (void)hipFree(h->c.partials);
   if (h->ctl_dev) (void)hipFree(h->ctl_dev);
   if (h->res) (void)hipHostFree(h->res);
   delete h;
@@ -92,38 +88,22 @@ extern "C" int mi_ode_linadj_create(const mi_ode_linadj_desc* desc, mi_ode_linad
   if (tb.n_stages != kLaS || !tb.fsal) {
     mi_set_error("linear adjoint: a 6-row FSAL-shaped tableau (dopri5) only - other methods take the generic path"); return MI_ODE_E_INVALID;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); mi_set_error("no HIP device"); return MI_ODE_E_NODEVICE; }
   mi_ode_linadj* h = new mi_ode_linadj();
   memset(h, 0, sizeof(*h));
+  HandoffHost& c = h->c;
   h->d = *desc;
   h->is_f32 = desc->dtype == MI_ODE_F32;
   h->elt = h->is_f32 ? 4 : 8;
   h->dp = la_pad_dim(desc->dim);
-  h->fn = h->is_f32 ? la_fn<float>(h->dp, &h->lds, &h->block) : la_fn<double>(h->dp, &h->lds, &h->block);
+  h->fn = h->is_f32 ? la_fn<float>(h->dp, &c.lds, &c.block) : la_fn<double>(h->dp, &c.lds, &c.block);
   h->ntiles = (desc->batch + 15) / 16;
-  int dev = 0, cus = 0, per_cu = 0;
-  {                                              // (h is released on these early returns too)
-    hipError_t e0 = hipGetDevice(&dev);
-    if (e0 == hipSuccess) e0 = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e0 != hipSuccess) {
-      mi_set_error("mi_ode_linadj_create: device query failed: %s", hipGetErrorString(e0));
-      (void)hipGetLastError();
-      delete h; return MI_ODE_E_HIP;
-    }
-  }
-  if (hipFuncSetAttribute(h->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess) (void)hipGetLastError();
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->fn, h->block, h->lds) != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    mi_set_error("linear adjoint kernel does not fit a compute unit (LDS %zu bytes, %d threads)", h->lds, h->block);
-    delete h; return MI_ODE_E_HIP;
-  }
-  long long g = h->ntiles;                       // every workgroup co-resident (the hand-offs spin): at most one per CU
-  if (g > cus) g = cus;
-  if (g > kLaMaxG) g = kLaMaxG;
+  int cus = 0;
+  const int rc = handoff_device(&h->fn, 1, c.block, c.lds, &cus, "linear adjoint");
+  if (rc != 0) { mi_ode_linadj_destroy(h); return rc; }
+  int g = handoff_cap_grid(h->ntiles, cus, kLaMaxG);
   if (g < 1) g = 1;
   if (const char* eg = getenv("MI_ODE_LINADJ_GRID")) { const int v = atoi(eg); if (v >= 1 && v <= g) g = v; }   // tests: other grids
-  h->grid = (int)g;
+  c.grid = g;
   const size_t D = (size_t)h->dp, E = D * D + D;
   const size_t n = (size_t)desc->batch * (size_t)desc->dim;
   h->stride = (long long)((n * h->elt + 255) / 256 * 256);
@@ -135,13 +115,13 @@ extern "C" int mi_ode_linadj_create(const mi_ode_linadj_desc* desc, mi_ode_linad
   if (e == hipSuccess) e = hipMalloc((void**)&h->mmat, kLaPP * E * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&h->theta, 2 * E * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&h->ktab, 4 * kLaPP * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&h->gpart, (size_t)h->grid * E * h->elt);
+  if (e == hipSuccess) e = hipMalloc((void**)&h->gpart, (size_t)c.grid * E * h->elt);
   if (e == hipSuccess) e = hipMalloc((void**)&h->wpad, 2 * D * D * h->elt);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->partials, (size_t)kMaxBlocks * kRec * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&h->ctl_dev, sizeof(Ctl));
   if (e == hipSuccess) e = hipHostMalloc((void**)&h->res, sizeof(LinAdjResult), hipHostMallocDefault);
   if (e == hipSuccess && getenv("MI_ODE_LINADJ_PROF") != nullptr) e = hipMalloc((void**)&h->skew, 32 * (size_t)kLaMaxG * 2 * sizeof(long long));
-  if (e == hipSuccess) e = hipMemset(h->partials, 0, (size_t)kMaxBlocks * kRec * sizeof(double));
+  e = handoff_alloc(c, e, 1 << 20);              // an attempt of the two systems lasts a fraction of a millisecond; the first hand-off comes
+                                                 // after a tile pass and a slab pass
   if (e == hipSuccess) e = hipMemset(h->mmat, 0, kLaPP * E * sizeof(double));      // the bias rows of M_pq, p > 0, stay zero
   if (e == hipSuccess) e = hipMemset(h->cvec, 0, kLaP * D * sizeof(double));
   if (e == hipSuccess) e = hipMemset(h->lmat, 0, kLaP * D * D * sizeof(double));
@@ -166,13 +146,6 @@ extern "C" int mi_ode_linadj_create(const mi_ode_linadj_desc* desc, mi_ode_linad
     return MI_ODE_E_HIP;
   }
   memset(h->res, 0, sizeof(LinAdjResult));
-  h->seq = 0;
-  h->spin_limit = 1 << 20;                       // an attempt of the two systems lasts a fraction of a millisecond: skew bound, not a time-out to hit
-  h->spin_first = 1 << 14;                       // residency check (the first hand-off comes after a tile pass and a slab pass)
-  if (const char* e3 = getenv("MI_ODE_PERSIST_SPIN_FIRST")) h->spin_first = atoi(e3);
-  if (const char* e2 = getenv("MI_ODE_PERSIST_SPIN_LIMIT")) h->spin_limit = atoi(e2);
-  h->sleep_first = h->grid <= 32 ? 16 : 32;
-  h->sleep_poll = 2;
   *out = h;
   return 0;
 }
@@ -191,37 +164,21 @@ extern "C" int mi_ode_linadj_segment(mi_ode_linadj_handle h, const void* w_dev, 
   LinAdjArgs A;
   memset(&A, 0, sizeof(A));
   StepArgs& S = A.p.s;
-  const mi_ode_tableau& tb = h->d.tableau;
   S.ctl = h->ctl_dev; S.batch = h->d.batch; S.dim = h->d.dim; S.n_plane = h->d.batch * (long long)h->d.dim;
   S.interp = MI_ODE_INTERP_QUARTIC_MID;
-  for (int i = 0; i < kLaS; ++i) {
-    S.alpha[i] = tb.alpha[i];
-    for (int j = 0; j <= i; ++j) S.beta[i][j] = tb.beta[i][j];
-  }
-  for (int j = 0; j <= kLaS; ++j) { S.e[j] = tb.c_error[j]; S.cmid[j] = tb.c_mid[j]; S.csol[j] = tb.c_sol[j]; }
-  S.partials = h->partials;
+  fill_tableau(S, h->d.tableau, kLaS);
   S.out = adj_y_out_dev;
   const bool reversed = t_end < t_start;          // misc.py:311-321: t <- -t, f <- -f(-t, y)
   S.rhs.w[0] = w_dev; S.rhs.b[0] = b_dev;
   S.rhs.sign = reversed ? -1.0 : 1.0;
-  CtrlParams& cp = S.cp;
-  cp.rtol = h->d.rtol; cp.atol = h->d.atol; cp.safety = h->d.safety; cp.ifactor = h->d.ifactor; cp.dfactor = h->d.dfactor;
-  cp.inv_ifactor = 1.0 / h->d.ifactor; cp.inv_dfactor = 1.0 / h->d.dfactor;
-  cp.max_num_steps = h->d.max_num_steps > 0 ? h->d.max_num_steps : 2147483647LL;
-  cp.n_local = S.n_plane;
-  cp.order = h->d.order; cp.init_order = h->d.init_order;
-  cp.controller = MI_ODE_CTRL_MISC; cp.is_f32 = h->is_f32; cp.n_stages = kLaS; cp.auto_first_step = 1;
+  fill_ctrl(S.cp, h->d, S.n_plane, h->is_f32, kLaS);
   A.p.t0 = reversed ? -t_start : t_start;
   A.t_end = reversed ? -t_end : t_end;
   A.p.t_small[0] = A.t_end;
   A.p.n_out = 1;
-  A.p.world = 1;
   A.p.nseg = 1;
-  A.p.seq_base = h->seq;
-  A.p.spin_limit = h->spin_limit;
-  A.p.xspin_limit = h->spin_limit;
-  A.p.spin_first = h->spin_first < h->spin_limit ? h->spin_first : h->spin_limit;
-  A.p.sleep_first = h->sleep_first; A.p.sleep_poll = h->sleep_poll;
+  handoff_fill(A.p, h->c);
+  A.p.xspin_limit = h->c.spin_limit;
   A.y_in = y_dev; A.a_in = adj_y_dev; A.th_in = adj_params_dev; A.adjt_in = adj_t_dev;
   A.th_out = adj_params_out_dev; A.adjt_out = adj_t_out_dev;
   A.grad_in = grad_out_dev; A.dldt_out = dldt_out_dev;
@@ -235,23 +192,21 @@ extern "C" int mi_ode_linadj_segment(mi_ode_linadj_handle h, const void* w_dev, 
   memset(h->res, 0, sizeof(LinAdjResult));
   h->res->status = MI_ODE_ST_SYNC_TIMEOUT;       // (overwritten by the kernel's result record)
   void* args[] = {(void*)&A};
-  hipError_t e = hipLaunchKernel(h->fn, dim3((unsigned)h->grid), dim3((unsigned)h->block), args, h->lds, st);
+  hipError_t e = hipLaunchKernel(h->fn, dim3((unsigned)h->c.grid), dim3((unsigned)h->c.block), args, h->c.lds, st);
   if (e != hipSuccess) { mi_set_error("linear adjoint kernel launch failed: %s", hipGetErrorString(e)); (void)hipGetLastError(); return MI_ODE_E_HIP; }
   h->n_launches += 1;
   {
     const hipError_t es = hipStreamSynchronize(st);          // the kernel's last act was the zero-copy store of its result record
     if (es != hipSuccess) {
       // the aborted launch may have written records and flags under this call's stamps: the next segment must not reuse them
-      h->seq += 4096u;
-      if (h->seq >= 0xE0000000u) h->seq = 0;
+      handoff_advance(h->c, 4096u);
       mi_set_error("hipStreamSynchronize after the linear adjoint kernel failed: %s", hipGetErrorString(es));
       (void)hipGetLastError();
       return MI_ODE_E_HIP;
     }
   }
   const LinAdjResult r = *h->res;
-  h->seq += (unsigned)(r.handoffs > 0 ? r.handoffs : 64) + 16u;
-  if (h->seq >= 0xE0000000u) h->seq = 0;
+  handoff_advance(h->c, (unsigned)(r.handoffs > 0 ? r.handoffs : 64) + 16u);
   if (getenv("MI_ODE_LINADJ_PROF") != nullptr)
     fprintf(stderr, "[linadj prof] attempts %lld (accepted %lld) hand-offs %d  us: tile passes %.1f (matrix loads %.1f, before %.1f, block reduce %.1f)  theta combinations %.1f  "
             "attempt hand-offs %.1f  small products: flag waits %.1f L %.1f M %.1f | prologue: init + first step size + first L_p %.1f f0 passes %.1f power levels %.1f slab %.1f first hand-off + barrier %.1f fold %.1f rest %.1f | epilogue %.1f\n",
@@ -259,7 +214,7 @@ extern "C" int mi_ode_linadj_segment(mi_ode_linadj_handle h, const void* w_dev, 
             0.01 * r.prof[12], 0.01 * r.prof[13], 0.01 * r.prof[5], 0.01 * r.prof[14], 0.01 * r.prof[15], 0.01 * r.prof[3], 0.01 * r.prof[4], 0.01 * r.prof[11], 0.0, 0.01 * r.prof[6]);
   if (h->skew != nullptr && getenv("MI_ODE_LINADJ_PROF") != nullptr) {
     static long long stamps[32 * kLaMaxG * 2];
-    const int G = h->grid;
+    const int G = h->c.grid;
     if (hipMemcpy(stamps, h->skew, sizeof(long long) * 32 * G * 2, hipMemcpyDeviceToHost) == hipSuccess) {
       for (int g = 0; g < 32; ++g) {
         long long a_min = (1LL << 62), a_max = 0, l_min = (1LL << 62), l_max = 0; double a_sum = 0; int n = 0, last = -1;
@@ -281,11 +236,7 @@ extern "C" int mi_ode_linadj_segment(mi_ode_linadj_handle h, const void* w_dev, 
   }
   if (host_scalars != nullptr) { host_scalars[0] = r.dldt; host_scalars[1] = r.adjt_end; }
   if (stats != nullptr) {
-    memset(stats, 0, sizeof(*stats));
-    stats->n_attempts = r.n_attempt; stats->n_accepted = r.n_accept; stats->n_rejected = r.n_attempt - r.n_accept;
-    stats->nfe = 2 + 6 * r.n_attempt;
-    stats->t = reversed ? -r.t1 : r.t1; stats->dt = r.dt; stats->last_ratio = r.ratio; stats->status = r.status;
-    stats->n_polls = 1; stats->n_launches = 1;
+    handoff_stats(stats, r, reversed);
     stats->clock_mhz = r.clk_ticks > 0 ? 100.0 * (double)r.clk_cycles / (double)r.clk_ticks : 0.0;
   }
   return (int)r.status;

@@ -40,15 +40,10 @@ int rows_ensure_t_out(mi_ode_solver* h, int n) {
 
 // tableau, right-hand side and controller parameters of the handle, as the shared kernels get them
 void rows_step_args(mi_ode_solver* h, StepArgs& A) {
-  const mi_ode_tableau& tb = h->d.tableau;
   memset(&A, 0, sizeof(A));
   A.ctl = h->ctl; A.planes = h->planes; A.stride = h->stride; A.batch = h->d.batch; A.dim = (int)h->d.dim;
   A.interp = h->d.interp; A.out = h->cur_out; A.t_out = h->t_out_dev; A.n_plane = h->n;
-  for (int i = 0; i < h->S; ++i) {
-    A.alpha[i] = tb.alpha[i];
-    for (int j = 0; j <= i; ++j) A.beta[i][j] = tb.beta[i][j];
-  }
-  for (int j = 0; j <= h->S; ++j) { A.e[j] = tb.c_error[j]; A.cmid[j] = tb.c_mid[j]; A.csol[j] = tb.c_sol[j]; }
+  fill_tableau(A, h->d.tableau, h->S);
   A.partials = h->partials; A.rhs = h->rhs;
   A.ticket = nullptr;
   A.cp = h->cp;

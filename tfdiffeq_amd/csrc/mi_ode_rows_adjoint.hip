@@ -62,23 +62,10 @@ extern "C" int mi_ode_adjoint_rows(const mi_ode_adjoint_rows_desc* desc, const m
   memset(&A, 0, sizeof(A));
   StepArgs& s = A.s;
   s.batch = d.batch; s.dim = d.dim; s.n_plane = d.batch * d.dim; s.interp = MI_ODE_INTERP_QUARTIC_MID;
-  for (int i = 0; i < S; ++i) {
-    s.alpha[i] = tb.alpha[i];
-    for (int j = 0; j <= i; ++j) s.beta[i][j] = tb.beta[i][j];
-  }
-  for (int j = 0; j <= S; ++j) { s.e[j] = tb.c_error[j]; s.cmid[j] = tb.c_mid[j]; s.csol[j] = tb.c_sol[j]; }
-  memcpy(s.rhs.s, rhs->scalars, sizeof(s.rhs.s));
-  for (int i = 0; i < 3; ++i) { s.rhs.w[i] = rhs->w[i]; s.rhs.b[i] = rhs->b[i]; }
+  fill_tableau(s, tb, S);
+  fill_rhs(s.rhs, *rhs);
   s.rhs.sign = 1.0;                                          // (the kernel reverses time itself)
-  s.rhs.hidden = rhs->hidden;
-  CtrlParams& cp = s.cp;
-  cp.rtol = d.rtol; cp.atol = d.atol; cp.safety = d.safety; cp.ifactor = d.ifactor; cp.dfactor = d.dfactor;
-  cp.inv_ifactor = 1.0 / d.ifactor; cp.inv_dfactor = 1.0 / d.dfactor;
-  cp.max_num_steps = d.max_num_steps > 0 ? d.max_num_steps : 2147483647LL;
-  cp.n_local = d.dim;
-  cp.order = d.order; cp.init_order = d.init_order;
-  cp.controller = MI_ODE_CTRL_MISC; cp.is_f32 = d.dtype == MI_ODE_F32 ? 1 : 0; cp.n_stages = S; cp.auto_first_step = 1;
-  cp.t_out = nullptr;                                        // (set per interval, by the row)
+  fill_ctrl(s.cp, d, d.dim, d.dtype == MI_ODE_F32 ? 1 : 0, S);   // (cp.t_out stays null: set per interval, by the row)
   A.ans = ans_dev; A.g = grad_ans_dev; A.grad_y0 = grad_y0_out_dev;
   A.row_params = d.row_params_dev; A.row_tvjp = d.row_time_vjps_dev; A.row_counts = (long long*)d.row_counts_dev;
   A.row_status = (long long*)d.row_status_dev;

@@ -35,8 +35,8 @@ GRID_BYTES), places the output gradients on the grid (_grid_plan) and runs the e
 does all of it in ONE launch without a stored trajectory ('fused linear sweep (own grid)', GRID_KERNEL).  Adaptive solves over a recorded
 step sequence, the multistep family, grid_constructor and eps != 0 are not covered: they raise ValueError and name `odeint_adjoint`.
 
-Layout: the engines that own a native handle (_FusedDiscreteEngine / ...64, _FusedLinearEngine, _FusedLinearGridEngine) share _SweepEngine
-(create, close, the status of a sweep) and the size-4 cache rule of _cached.  `odeint_discrete` plans a call ONCE, in the order own-grid
+Layout: the engines that own a native handle (_FusedDiscreteEngine / ...64, _FusedLinearEngine, _FusedLinearGridEngine) share engine._SweepEngine
+(create, close, the status of a sweep) and the size-4 cache rule of engine._cached, as the adjoint engines do.  `odeint_discrete` plans a call ONCE, in the order own-grid
 linear kernel, linear sweep, row-local sweep, float64 mlp check - each for the trajectory length the backward will sweep - and hands the
 outcome to _OdeintDiscretePlanned as one _Plans record; with every switch off it calls plain _OdeintDiscrete.
 """
@@ -46,6 +46,7 @@ import ctypes as C
 import torch
 
 from . import _native as N
+from .engine import HandoffTimeout, _SweepEngine, _cached
 from .fixed_grid import Euler, RK4
 from .odeint import _graph_leaves, odeint
 from .rk_common import _ButcherTableau
@@ -170,62 +171,6 @@ def generic_sweep(func, params, ys, t, grad_ys, method):
     return lam, gp
 
 
-class _SweepEngine(object):
-    """Owns one handle of a one-launch sweep: the library, the device, the descriptor, the stats of the last sweep.  A subclass names its
-    create and destroy symbols, fills its descriptor and says what a sweep passes."""
-    _create = _destroy = None
-
-    def _open(self, device, desc, method, *create_args):
-        """The handle of `desc` (its tableau: `method`'s) on `device`; create_args go between the descriptor and the handle."""
-        from .solvers import _fill_tableau
-        self.lib = N.load()
-        self.device = torch.device(device)
-        _fill_tableau(desc.tableau, TABLEAUS[method], None)
-        self.desc = desc
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            N.check(getattr(self.lib, self._create)(C.byref(desc), *(create_args + (C.byref(h),))), self._create)
-        self.h = h
-        self.stats = N.Stats()
-
-    def close(self):
-        if getattr(self, 'h', None):
-            getattr(self.lib, self._destroy)(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _run(self, name, args, value):
-        """The sweep `name` of this handle with `args`, the stats and the stream: `value`, or HandoffTimeout / AssertionError for the
-        status it returned."""
-        with torch.cuda.device(self.device):
-            rc = N.check(getattr(self.lib, name)(self.h, *(tuple(args) + (C.byref(self.stats), N.stream_ptr(self.device)))), name)
-        if rc != 0:
-            from .adjoint import HandoffTimeout
-            if rc & N.ST_SYNC_TIMEOUT:
-                raise HandoffTimeout(N.status_message(rc))
-            raise AssertionError(N.status_message(rc))
-        return value
-
-
-def _cached(cache, key, make, close_on_evict):
-    """The engine of `key` in `cache`, four cached at most, the oldest evicted - only after a successful make(): a refusal must not cost
-    live engines.  close_on_evict: the evicted engine is closed; otherwise only the cache's reference is dropped."""
-    eng = cache.get(key)
-    if eng is None:
-        eng = make()
-        while len(cache) >= 4:
-            old = cache.pop(next(iter(cache)))
-            if close_on_evict:
-                old.close()
-        cache[key] = eng
-    return eng
-
-
 class _FusedDiscreteEngine(_SweepEngine):
     """Owns one mi_ode_discrete handle: the reverse sweep of `n_points - 1` steps of `method` for a [batch, dim] state in `dtype` and the
     dim -> hidden -> hidden -> dim MLP (time_dependent: (1 + dim) -> hidden, the first layer sees concat([t, x])), one launch."""
@@ -236,7 +181,7 @@ class _FusedDiscreteEngine(_SweepEngine):
         d = N.DiscreteDesc()
         d.batch, d.dim, d.hidden = int(batch), int(dim), int(hidden)
         d.n_points, d.chunk_tiles = int(n_points), int(chunk_tiles)
-        self._open(device, d, method, 1 if time_dependent else 0)
+        self._open(device, d, TABLEAUS[method], None, 1 if time_dependent else 0)
         self.batch, self.dim, self.n_points, self.time_dependent = int(batch), int(dim), int(n_points), bool(time_dependent)
         self.n_params = int(getattr(self.lib, self._num_params)(self.h))
 
@@ -362,7 +307,7 @@ class _FusedLinearEngine(_SweepEngine):
         self.dtype = dtype
         d = N.DiscreteLinearDesc()
         d.dtype, d.dim, d.batch, d.has_bias, d.n_points = N.dtype_code(dtype), int(dim), int(batch), int(bool(has_bias)), int(n_points)
-        self._open(device, d, method)
+        self._open(device, d, TABLEAUS[method], None)
         self.batch, self.dim, self.n_points, self.has_bias = int(batch), int(dim), int(n_points), bool(has_bias)
 
     def profile(self):
@@ -398,7 +343,7 @@ class _FusedLinearGridEngine(_SweepEngine):
         d = N.DiscreteLinearGridDesc()
         d.dtype, d.dim, d.batch, d.has_bias = N.dtype_code(dtype), int(dim), int(batch), int(bool(has_bias))
         d.n_steps, d.n_out = int(n_steps), int(n_out)
-        self._open(device, d, method)
+        self._open(device, d, TABLEAUS[method], None)
         self.batch, self.dim, self.n_steps, self.n_out, self.has_bias = int(batch), int(dim), int(n_steps), int(n_out), bool(has_bias)
 
     def profile(self):
@@ -706,7 +651,6 @@ def _stored_sweep(ctx, t, ans, grad_output):
     n_steps = int(like.shape[0]) - 1
     lin, lin_why = getattr(ctx, 'linear_plan', None) or (None, '')
     if lin is not None:
-        from .adjoint import HandoffTimeout
         try:
             with torch.no_grad():
                 g_y0, gp = lin.sweep(t.to(like.dtype).double().cpu().numpy(), like, grad_output[0], len(params))
@@ -733,7 +677,7 @@ def _stored_sweep(ctx, t, ans, grad_output):
     if lin_why:
         why = 'fused linear sweep: %s; %s' % (lin_why, why if row_why else 'fused mlp sweep: ' + why)
     if plan is not None:
-        from .adjoint import HandoffTimeout, canonical_to_module_order
+        from .adjoint import canonical_to_module_order
         eng, mlp = plan
         try:
             with torch.no_grad():
@@ -774,7 +718,6 @@ def _own_grid_sweep(ctx, gplan, y0, grad_output):
     n_steps, n_out = int(grid.shape[0]) - 1, len(gplan.out_step)
     kern, kern_why = getattr(ctx, 'linear_grid_plan', None) or (None, '')
     if kern is not None:
-        from .adjoint import HandoffTimeout
         try:
             with torch.no_grad():
                 g_y0, gp = kern.sweep_grid(gplan, y0[0], grad_output[0], len(params))

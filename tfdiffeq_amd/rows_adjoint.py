@@ -177,9 +177,7 @@ def run_backward(plan_, t, ans, grad_ans):
     if bad:
         first = bad[0]
         bits = int(row_status[first])
-        msg = N.status_message(bits)
-        if bits & N.ST_MAX_STEPS:
-            msg = 'max_num_steps exceeded ({}>={})'.format(cfg['max_num_steps'], cfg['max_num_steps'])       # dopri5.py:85
+        msg = N.status_text(bits, cfg['max_num_steps'])          # dopri5.py:85 (a row's step size is not reported: the library's text)
         raise AssertionError('%s [per_trajectory adjoint: %d of %d rows failed; rows %s%s, the message is row %d\'s]' % (
             msg, len(bad), batch, ', '.join(str(i) for i in bad[:8]), ', ...' if len(bad) > 8 else '', first))
     return g_y0, g_th[:P], g_t, rows, int(stats.n_launches)

@@ -302,14 +302,9 @@ class _FusedEngine(object):
     def _raise_for_status(self, bits):
         if bits == 0:
             return
-        msg = N.status_message(bits)
         if bits & N.ST_SYNC_TIMEOUT:       # engine fault, not one of the reference's assertions
-            raise SyncTimeout(msg + " - retry with options={'fusion': 'step'}")
-        if bits & N.ST_MAX_STEPS:
-            msg = 'max_num_steps exceeded ({}>={})'.format(self.desc.max_num_steps, self.desc.max_num_steps)
-        if bits & N.ST_DT_UNDERFLOW:
-            msg = 'underflow in dt {}'.format(self.stats.dt)
-        raise AssertionError(msg)          # the reference raises AssertionError for all of these
+            raise SyncTimeout(N.status_message(bits) + " - retry with options={'fusion': 'step'}")
+        raise AssertionError(N.status_text(bits, self.desc.max_num_steps, self.stats.dt))   # the reference raises AssertionError for all of these
 
     def _check_y0(self, y0):
         if y0 is None:
@@ -938,12 +933,7 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
         _credit_nfe(self.func, int(st['nfe']) - py_calls)
         bits = int(st['status'])
         if bits:
-            msg = N.status_message(bits)
-            if bits & N.ST_MAX_STEPS:
-                msg = 'max_num_steps exceeded ({}>={})'.format(self.max_num_steps, self.max_num_steps)
-            if bits & N.ST_DT_UNDERFLOW:
-                msg = 'underflow in dt {}'.format(st['dt'])
-            raise AssertionError(msg)                 # dopri5.py:85-100
+            raise AssertionError(N.status_text(bits, self.max_num_steps, st['dt']))     # dopri5.py:85-100
         return outs
 
     # -- plane-kernel path (any callable, tuple states) -------------------------------------------
