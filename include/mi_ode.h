@@ -262,6 +262,20 @@ int mi_ode_integrate(mi_ode_handle h, const void* y0_dev, const double* t_host, 
  * bits (>= 0) or an error (< 0). */
 int mi_ode_integrate_rows(mi_ode_handle h, const void* rows_plugin, const void* y0_dev, const double* t_host, int32_t T,
                           void* out_dev, int64_t* row_stats_dev, mi_ode_stats* stats, void* stream);
+/* The same with output times, lengths and tolerances of every row's own (csrc/mi_ode_rows_t.h).  Row i of out_dev is what
+ * mi_ode_integrate returns for y0[i] alone with the times t_dev[i][0 .. len_i - 1] on a handle whose rtol / atol are rtol_dev[i] /
+ * atol_dev[i], bit for bit; out_dev[k][i] for k >= len_i is exactly 0 and t_dev[i][len_i ..] is never read.
+ *   h, row_stats_dev, stats, the return value: as for mi_ode_integrate_rows (stats->t is 0: every row ends at a time of its own)
+ *   rows_t_plugin the table mi_ode_rows_t_plugin_get(dtype) of the plugin's rows-t shared object returned
+ *                 (csrc/mi_ode_rows_t_plugin.h) when the handle's right-hand side is a row-local plugin; NULL for the catalogue systems
+ *   t_dev         DEVICE [batch][T] float64, every row strictly increasing over its own length (the caller checks that: nothing of
+ *                 it is read on the host; times that are not can give wrong numbers or a status bit, never an unbounded loop)
+ *   len_dev       DEVICE [batch] int32 with values in 1 .. T (clamped to that range by the kernel), or NULL: every row has T times
+ *   rtol_dev, atol_dev   DEVICE [batch] float64 each, or NULL: the handle's value for every row
+ * One launch and one synchronisation, as there. */
+int mi_ode_integrate_rows_t(mi_ode_handle h, const void* rows_t_plugin, const void* y0_dev, const double* t_dev, int32_t T,
+                            const int32_t* len_dev, const double* rtol_dev, const double* atol_dev, void* out_dev,
+                            int64_t* row_stats_dev, mi_ode_stats* stats, void* stream);
 /* FixedGridODESolver.integrate(t) with grid = t (solvers.py:82-104); no host synchronisation inside. */
 int mi_ode_fixed_grid_integrate(mi_ode_handle h, const void* y0_dev, const double* t_host, int32_t T,
                                 void* out_dev, mi_ode_stats* stats, void* stream);
@@ -528,6 +542,40 @@ typedef struct mi_ode_adjoint_rows_desc {
 int mi_ode_adjoint_rows(const mi_ode_adjoint_rows_desc* desc, const mi_ode_rhs* rhs, const void* ans_dev, const void* grad_ans_dev,
                         void* grad_y0_out_dev, void* grad_params_out_dev, void* grad_t_out_dev, mi_ode_stats* stats, void* stream);
 int64_t mi_ode_adjoint_rows_sizeof(void);                 /* sizeof(mi_ode_adjoint_rows_desc), for a binding's layout check */
+
+/* The same for a solve with output times, lengths and tolerances of every row's own (mi_ode_integrate_rows_t;
+ * csrc/mi_ode_rows_adjoint_t.h).  Row i is what mi_ode_adjoint_rows returns for row i alone with the times t[i][0 .. len_i - 1] at
+ * rtol_dev[i] / atol_dev[i], bit for bit.  rhs: MI_ODE_RHS_PLUGIN with `plugin` = what a rows-adjoint-t plugin's
+ * mi_ode_rows_adjoint_t_plugin_get(dtype) returned (csrc/mi_ode_rows_adjoint_t_plugin.h).  Limits as there. */
+typedef struct mi_ode_adjoint_rows_t_desc {
+  int32_t dtype;              /* MI_ODE_F32 / MI_ODE_F64 */
+  int32_t n_times;            /* T >= 1: the second axis of the times, the longest row */
+  int64_t batch;
+  int32_t dim;                /* the plugin's */
+  int32_t n_params;           /* P: trainable elements, the plugin's */
+  int32_t order, init_order;  /* dopri5: 5, 4; bosh3: 3, 2 */
+  double rtol, atol;          /* adjoint_rtol / adjoint_atol of every row without a value of its own (rtol_dev / atol_dev NULL) */
+  double safety, ifactor, dfactor;
+  int64_t max_num_steps;      /* <= 0: 2^31 - 1 */
+  mi_ode_tableau tableau;
+  const double* neg_t_dev;    /* device [batch][T]: every row's output times, NEGATED; row i is read up to len_i - 1 only */
+  const int32_t* len_dev;     /* device [batch] with values in 1 .. T (clamped to that range by the kernel), or NULL: every row has T times */
+  const double* rtol_dev;     /* device [batch] float64, or NULL */
+  const double* atol_dev;     /* device [batch] float64, or NULL */
+  void* row_params_dev;       /* out [batch, max(P, 1)]: every row's own adj_params */
+  void* row_time_vjps_dev;    /* out [batch, T]: every row's own time vjps, exact zeros from len_i on - the gradient of `t`, not summed */
+  int64_t* row_counts_dev;    /* out [batch, 3, T - 1]: as mi_ode_adjoint_rows_desc; zeros for the intervals beyond len_i - 1 */
+  int64_t* row_status_dev;    /* out [batch]: MI_ODE_ST_* bits of the row */
+  void* partials_dev;         /* workspace: ceil(batch / 256) * max(P, 1) elements of the state dtype */
+  void* ticket_dev;           /* one zeroed 32-bit word (left zero again) */
+} mi_ode_adjoint_rows_t_desc;
+/* ans_dev / grad_ans_dev [T, batch, dim]: grad_ans_dev[k][i] for k >= len_i is never read; grad_y0_out_dev [batch, dim];
+ * grad_params_out_dev [max(P, 1)]: the rows summed in the fixed order of mi_ode_adjoint_rows - two calls give identical bits.  Enqueues
+ * one launch on `stream` and returns 0 without waiting, or a negative MI_ODE_E_* as mi_ode_adjoint_rows does; a failing row is reported
+ * in row_status_dev. */
+int mi_ode_adjoint_rows_t(const mi_ode_adjoint_rows_t_desc* desc, const mi_ode_rhs* rhs, const void* ans_dev, const void* grad_ans_dev,
+                          void* grad_y0_out_dev, void* grad_params_out_dev, mi_ode_stats* stats, void* stream);
+int64_t mi_ode_adjoint_rows_t_sizeof(void);               /* sizeof(mi_ode_adjoint_rows_t_desc), for a binding's layout check */
 
 /* ---- (A'''''') the same reverse sweep for the linear system f(y) = y W (+ b) on the matrix cores, ONE launch ------------------------ */
 /* The transpose of the fixed-grid map of MI_ODE_RHS_LINEAR (csrc/mi_ode_discrete_linear.h): Ybar_i = kbar_i W^T, Wbar += Y_i^T kbar_i,

@@ -119,6 +119,16 @@ class AdjointRowsDesc(C.Structure):
 ROWS_ADJOINT_MAX_AUG, ROWS_ADJOINT_THREADS = 32, 256
 
 
+class AdjointRowsTDesc(C.Structure):
+    """mi_ode_adjoint_rows_t_desc: the same with every row's own output times, length and tolerances."""
+    _fields_ = [('dtype', C.c_int32), ('n_times', C.c_int32), ('batch', C.c_int64), ('dim', C.c_int32), ('n_params', C.c_int32),
+                ('order', C.c_int32), ('init_order', C.c_int32), ('rtol', C.c_double), ('atol', C.c_double),
+                ('safety', C.c_double), ('ifactor', C.c_double), ('dfactor', C.c_double), ('max_num_steps', C.c_int64), ('tableau', Tableau),
+                ('neg_t_dev', C.c_void_p), ('len_dev', C.c_void_p), ('rtol_dev', C.c_void_p), ('atol_dev', C.c_void_p),
+                ('row_params_dev', C.c_void_p), ('row_time_vjps_dev', C.c_void_p), ('row_counts_dev', C.c_void_p),
+                ('row_status_dev', C.c_void_p), ('partials_dev', C.c_void_p), ('ticket_dev', C.c_void_p)]
+
+
 class DiscreteLinearDesc(C.Structure):
     """mi_ode_discrete_linear_desc: the reverse sweep of a fixed-grid solve of f(y) = y W (+ b) in one launch, on the matrix cores."""
     _fields_ = [('dtype', C.c_int32), ('dim', C.c_int32), ('batch', C.c_int64), ('has_bias', C.c_int32), ('n_points', C.c_int32),
@@ -201,6 +211,8 @@ _PROTOS = {
                                    C.POINTER(Stats), C.c_void_p]),
     'mi_ode_integrate_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_void_p,
                                         C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_integrate_rows_t': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     'mi_ode_fixed_grid_integrate': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p,
                                               C.POINTER(Stats), C.c_void_p]),
     'mi_ode_fixed_grid_integrate_on': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.c_int32,
@@ -252,6 +264,9 @@ _PROTOS = {
     'mi_ode_adjoint_rows': (C.c_int, [C.POINTER(AdjointRowsDesc), C.POINTER(Rhs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(Stats), C.c_void_p]),
     'mi_ode_adjoint_rows_sizeof': (C.c_int64, []),
+    'mi_ode_adjoint_rows_t': (C.c_int, [C.POINTER(AdjointRowsTDesc), C.POINTER(Rhs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_adjoint_rows_t_sizeof': (C.c_int64, []),
     'mi_ode_discrete_linear_create': (C.c_int, [C.POINTER(DiscreteLinearDesc), C.POINTER(C.c_void_p)]),
     'mi_ode_discrete_linear_destroy': (C.c_int, [C.c_void_p]),
     'mi_ode_discrete_linear_sweep': (C.c_int, [C.c_void_p, C.POINTER(Rhs), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -353,6 +368,8 @@ def load():
                               % (st.__name__, lib.mi_ode_sizeof(which), C.sizeof(st)))
     if lib.mi_ode_adjoint_rows_sizeof() != C.sizeof(AdjointRowsDesc):
         raise NativeError('struct layout mismatch for AdjointRowsDesc: C %d vs ctypes %d' % (lib.mi_ode_adjoint_rows_sizeof(), C.sizeof(AdjointRowsDesc)))
+    if lib.mi_ode_adjoint_rows_t_sizeof() != C.sizeof(AdjointRowsTDesc):
+        raise NativeError('struct layout mismatch for AdjointRowsTDesc: C %d vs ctypes %d' % (lib.mi_ode_adjoint_rows_t_sizeof(), C.sizeof(AdjointRowsTDesc)))
     _lib = lib
     return lib
 

@@ -136,7 +136,52 @@ def rows_refusal(func, y0, rows, fsal, *, quartic=True, force_planes=False, grou
     return ''
 
 
+ROWS_T_WHY = 'per-trajectory step control with per-row times, lengths or tolerances, one launch'
+# what a handle or descriptor is created with where every row brings a tolerance of its own (the kernels read the row's, never these)
+ROWS_T_RTOL0, ROWS_T_ATOL0 = 1e-6, 1e-9
+
+
+def _shape_of(x):
+    """The shape of a tensor or numpy array, None for anything else (a Python scalar; a tuple of tolerances keeps the reference's meaning:
+    one per component of a tuple state)."""
+    if isinstance(x, torch.Tensor) or type(x).__name__ == 'ndarray':
+        return tuple(x.shape)
+    return None
+
+
+def rows_t_wanted(t_shape, rtol_shape, atol_shape, has_lengths):
+    """True when an options['per_trajectory'] call goes to k_rows_rowlocal_t (csrc/mi_ode_rows_t.h): a 2-D `t`, or rtol / atol that are
+    not scalars.  A 1-D `t` with scalar tolerances is the shared-t call, as it was - with options['t_lengths'] a ValueError.  Pure: shapes only
+    (a scalar's is None or ())."""
+    if has_lengths and (t_shape is None or len(t_shape) != 2):
+        raise ValueError("options['t_lengths'] needs a 2-D `t` of shape [batch, T]: the lengths say how many of a row's own times count")
+    return (t_shape is not None and len(t_shape) >= 2) or any(s is not None and len(s) >= 1 for s in (rtol_shape, atol_shape))
+
+
+def rows_t_refusal(y_shape, t_shape, lengths_shape=None, lengths_is_int=True, rtol_shape=None, atol_shape=None,
+                   names=('rtol', 'atol')):
+    """'' when the per-row inputs of an options['per_trajectory'] call fit its state, else the reason the call is refused with.  Pure:
+    shapes and one dtype flag.  (Values - lengths in 1 .. T, monotone rows - are checked on the tensors: rows_times.prepare.)"""
+    if len(y_shape) != 2:
+        return ('per-row times, lengths or tolerances with a state of shape %s: row i of `t`, `rtol`, `atol` belongs to row i of a '
+                '[batch, dim] state' % (tuple(y_shape),))
+    batch = int(y_shape[0])
+    if len(t_shape) not in (1, 2) or (len(t_shape) == 2 and (int(t_shape[0]) != batch or int(t_shape[1]) < 1)):
+        return ('`t` of shape %s for a state of %d rows: a 2-D `t` is [batch, T] with T >= 1, row i the output times of row i'
+                % (tuple(t_shape), batch))
+    if lengths_shape is not None:
+        if not lengths_is_int:
+            return "options['t_lengths'] must be an integer tensor of shape [batch] (values in 1 .. T)"
+        if tuple(lengths_shape) != (batch,):
+            return "options['t_lengths'] of shape %s for a state of %d rows: one length per row, shape [batch]" % (tuple(lengths_shape), batch)
+    for name, shape in zip(names, (rtol_shape, atol_shape)):
+        if shape is not None and len(shape) >= 1 and tuple(shape) != (batch,):
+            return '`%s` of shape %s for a state of %d rows: a scalar, or one value per row, shape [batch]' % (name, tuple(shape), batch)
+    return ''
+
+
 ROWS_ADJOINT_WHY = 'per-trajectory adjoint: every row its own augmented solve with per-component control, one launch'
+ROWS_ADJOINT_T_WHY = 'per-trajectory adjoint over per-row times, lengths or tolerances: every row its own augmented solve, one launch'
 ROWS_ADJOINT_METHODS = ('dopri5', 'bosh3')
 
 

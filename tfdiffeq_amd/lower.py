@@ -2139,6 +2139,8 @@ class _GeneratedRHS(R.DeviceRHS):
     hyper_plugin = R.CustomRowLocal.hyper_plugin
     rows_source = R.CustomRowLocal.rows_source            # (row-local programs only, likewise: the per-trajectory kernel)
     rows_plugin = R.CustomRowLocal.rows_plugin
+    rows_t_source = R.CustomRowLocal.rows_t_source        # (... with per-row times, lengths and tolerances)
+    rows_t_plugin = R.CustomRowLocal.rows_t_plugin
 
     def fill(self, rhs, dtype, device):
         keep = super(_GeneratedRHS, self).fill(rhs, dtype, device)

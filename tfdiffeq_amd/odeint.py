@@ -55,6 +55,8 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     independent problems - row i of the result is what odeint(func, y0[i:i+1], t, ...) returns, every row with its own initial step, error
     ratio, accept / reject sequence and assertions, all in one launch (`odeint.last_stats['rows']`: per-row counts and status).  The default
     is the reference's semantics: one error norm and one step size for the whole batch.  What the mode cannot take raises ValueError.
+    In this mode `t` may be [batch, T] (every row its own output times; options['t_lengths'], an int tensor [batch], how many of them count)
+    and `rtol` / `atol` tensors [batch]: see `_odeint_per_trajectory`.
     """
     if options is not None and 'per_trajectory' in options:
         from .dispatch import per_trajectory_option
@@ -248,10 +250,31 @@ def _odeint_per_trajectory(func, y0, t, rtol, atol, method, options):
     """options={'per_trajectory': True}: row i of the result is what odeint(func, y0[i:i+1], t, ...) returns - every row of a [batch, dim]
     state with its own initial step, error ratio, accept / reject sequence, output cursor and assertions, all rows in ONE launch
     (csrc/mi_ode_rows.h).  A DeviceRHS goes to its solver (whose route refuses the families the kernel cannot take); a Python callable
-    reaches the kernel as a lowered row program.  Never answered with shared control."""
-    low, opts = _per_trajectory_target(func, y0, method, options)
+    reaches the kernel as a lowered row program.  Never answered with shared control.
+
+    Per-row inputs (csrc/mi_ode_rows_t.h, still one launch): `t` of shape [batch, T] - row i is then what
+    odeint(func, y0[i:i+1], t[i], ...) returns, the result is [T, batch, dim]; options['t_lengths'], an int tensor [batch] with values in
+    1 .. T - row i uses t[i, :len_i] only, solution[len_i:, i] is exactly 0 and t[i, len_i:] is never read; `rtol` / `atol` as tensors
+    [batch] (with a 1-D or a 2-D `t`) - row i at float(rtol[i]), float(atol[i]).  Every row strictly increasing, or every row strictly
+    decreasing, over its own length.  A 1-D `t` with scalar tolerances is the call above, unchanged."""
+    from . import rows_times
+    wanted, why = rows_times.shapes(y0, t, rtol, atol, options)            # (shapes only: refused before anything is traced)
+    if why:
+        raise ValueError("options['per_trajectory'] refused: " + why)
+    target_opts = {k: v for k, v in (options or {}).items() if k != 't_lengths'} if wanted else options
+    low, opts = _per_trajectory_target(func, y0, method, target_opts)
     if low is not None:
-        return _run_lowered(low, func, y0, t, rtol, atol, method, opts)
+        if wanted and 't_lengths' in options:
+            opts['t_lengths'] = options['t_lengths']
+        return _run_lowered(low, func, y0, t, rtol, atol, method, opts)     # (t, rtol, atol and the lengths travel as they are: the rows of the
+    if wanted:                                                              #  state keep their order under its reshape)
+        rt, _ = rows_times.prepare(y0, t, rtol, atol, options)
+        # misc._check_inputs on a stand-in for the direction the rows share: the sign goes to the right-hand side as for a 1-D t
+        tensor_input, f, state, _ = _check_inputs(func, y0, [0., -1.] if rt.decreasing else [0., 1.])
+        solver = SOLVERS[method](f, state, rtol=rt.rtol0, atol=rt.atol0, **opts)
+        solution = solver.integrate_rows_t(rt)
+        odeint.last_stats = getattr(solver, 'stats', {})
+        return solution[0] if tensor_input else solution
     tensor_input, f, state, tt = _check_inputs(func, y0, t)
     solver = SOLVERS[method](f, state, rtol=rtol, atol=atol, **opts)
     solution = solver.integrate(tt)

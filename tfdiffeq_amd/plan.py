@@ -107,11 +107,20 @@ def plan_rhs(rhs, y, solver, route, opts):
     return d
 
 
-def plan_rows(func, y0, rtol, atol, method, opts):
+def plan_rows(func, y0, rtol, atol, method, opts, t=None):
     """options['per_trajectory']: the per-trajectory kernel (csrc/mi_ode_rows.h) - or the reason the call is refused with (a ValueError
-    at the call: shared control is never substituted)."""
+    at the call: shared control is never substituted).  t: with a 2-D `t`, options['t_lengths'] or [batch] tolerances the kernel is
+    k_rows_rowlocal_t (csrc/mi_ode_rows_t.h); decided from shapes alone, as the call refuses them (values are checked by the call)."""
+    from . import rows_times
     from .odeint import SOLVERS, _per_trajectory_target
+    per_row_t = False
     try:
+        per_row_t, why = rows_times.shapes(y0, t, rtol, atol, opts)
+        if why:
+            raise ValueError("options['per_trajectory'] refused: " + why)
+        if per_row_t:
+            opts = {k: v for k, v in opts.items() if k != 't_lengths'}
+            rtol, atol = (D.ROWS_T_RTOL0 if D._shape_of(rtol) else rtol), (D.ROWS_T_ATOL0 if D._shape_of(atol) else atol)      # (the handle's: rows_times.prepare)
         low, run_opts = _per_trajectory_target(func, y0, method, opts)
         f, state = (func, y0) if low is None else (low.rhs, (y0[0] if isinstance(y0, (tuple, list)) else y0).reshape(low.state_shape))
         run_opts.pop('lower', None)
@@ -122,8 +131,10 @@ def plan_rows(func, y0, rtol, atol, method, opts):
         return {'engine': 'refused', 'kernel': None, 'launches': None, 'per_trajectory': True, 'why': str(e), 'lower': None}
     y, rhs, S = ys[0], route.rhs, len(solver.tableau.alpha)
     fam = D.family(rhs)
-    return {'engine': 'fused', 'kernel': 'k_rows_rowlocal<%s, %d, ..> (a trajectory per thread, any batch size, no grid hand-off)' % (TNAME[y.dtype], S),
-            'launches': 'one per call', 'why': D.ROWS_WHY, 'per_trajectory': True, 'family': FAMILY.get(fam, fam),
+    kernel, why = ('k_rows_rowlocal_t<%s, %d, ..> (a trajectory per thread with its own times, length and tolerances, any batch size, no grid hand-off)',
+                   D.ROWS_T_WHY) if per_row_t else ('k_rows_rowlocal<%s, %d, ..> (a trajectory per thread, any batch size, no grid hand-off)', D.ROWS_WHY)
+    return {'engine': 'fused', 'kernel': kernel % (TNAME[y.dtype], S),
+            'launches': 'one per call', 'why': why, 'per_trajectory': True, 'family': FAMILY.get(fam, fam),
             'state': '%d x %d %s' % (y.numel() // max(int(rhs.dim or 1), 1), rhs.dim, str(y.dtype).replace('torch.', '')),
             'lower': None if low is None else {'lowered': True, 'kind': low.kind, 'dim': low.dim, 'batch_axes': low.trace.nb}}
 
@@ -142,7 +153,7 @@ def plan(func, y0, t=None, rtol=1e-7, atol=1e-9, method=None, options=None, adjo
     opts = dict(options or {})
     opts, per_row = D.per_trajectory_option(opts)
     if per_row:
-        return plan_rows(func, y0, rtol, atol, method, opts)
+        return plan_rows(func, y0, rtol, atol, method, opts, t)
     mode = opts.pop('lower', LOWER_DEFAULT)
     tensor_input = isinstance(y0, torch.Tensor)
     ys = (y0,) if tensor_input else tuple(y0)

@@ -498,6 +498,25 @@ class CustomRowLocal(DeviceRHS):
             plugins[dtype] = hit
         return hit
 
+    def rows_t_source(self, dtype):
+        """The rows-t plugin of this system (csrc/mi_ode_rows_t_plugin.h): the same functor behind the per-trajectory kernel with per-row
+        times, lengths and tolerances."""
+        return rows_t_source_of(self.source(dtype))
+
+    def rows_t_plugin(self, dtype):
+        """(library, address of the mi_ode_rows_t_plugin table) for `dtype`; compiled once, cached by source and header hash."""
+        plugins = self.__dict__.setdefault('_rows_t_plugins', {})
+        hit = plugins.get(dtype)
+        if hit is None:
+            from . import _plugin_build
+            lib = _plugin_build.build_and_load(self.rows_t_source(dtype))
+            table = lib.mi_ode_rows_t_plugin_get(N.dtype_code(dtype))
+            if not table:
+                raise N.NativeError('rows-t plugin exports no table for %s' % dtype)
+            hit = (lib, int(table))
+            plugins[dtype] = hit
+        return hit
+
 
 _DISCRETE_PLUGINS = {}
 
@@ -548,6 +567,42 @@ def rows_source_of(rowlocal_source):
         raise ValueError('not a row-local plugin translation unit: the per-trajectory kernel takes one trajectory per thread')
     src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_rows_plugin.h"')
     return src.replace('MI_ODE_DEFINE_ROWLOCAL_PLUGIN(', 'MI_ODE_DEFINE_ROWS_PLUGIN(')
+
+
+def rows_t_source_of(rowlocal_source):
+    """A row-local plugin translation unit (mi_ode_plugin.h) turned into the rows-t plugin of the same functor (per-trajectory step control
+    with per-row times, lengths and tolerances)."""
+    if 'MI_ODE_DEFINE_ROWLOCAL_PLUGIN(' not in rowlocal_source:
+        raise ValueError('not a row-local plugin translation unit: the per-trajectory kernel takes one trajectory per thread')
+    src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_rows_t_plugin.h"')
+    return src.replace('MI_ODE_DEFINE_ROWLOCAL_PLUGIN(', 'MI_ODE_DEFINE_ROWS_T_PLUGIN(')
+
+
+def rows_adjoint_t_source_of(adjoint_source):
+    """A rows-adjoint plugin translation unit (lower.adjoint_source, mi_ode_rows_adjoint_plugin.h) turned into the rows-adjoint-t plugin of
+    the same functor (the per-trajectory adjoint with per-row times, lengths and tolerances)."""
+    if 'MI_ODE_DEFINE_ROWS_ADJOINT_PLUGIN(' not in adjoint_source:
+        raise ValueError('not a rows-adjoint plugin translation unit: the per-row adjoint kernel takes f with its generated vjp')
+    src = adjoint_source.replace('#include "mi_ode_rows_adjoint_plugin.h"', '#include "mi_ode_rows_adjoint_t_plugin.h"')
+    return src.replace('MI_ODE_DEFINE_ROWS_ADJOINT_PLUGIN(', 'MI_ODE_DEFINE_ROWS_ADJOINT_T_PLUGIN(')
+
+
+_ROWS_ADJOINT_T_PLUGINS = {}
+
+
+def rows_adjoint_t_plugin(source, dtype):
+    """(library, address of the mi_ode_rows_adjoint_t_plugin table) of a rows-adjoint-t translation unit (rows_adjoint_t_source_of);
+    compiled once, cached by source and header hash."""
+    hit = _ROWS_ADJOINT_T_PLUGINS.get((source, dtype))
+    if hit is None:
+        from . import _plugin_build
+        lib = _plugin_build.build_and_load(source)
+        table = lib.mi_ode_rows_adjoint_t_plugin_get(N.dtype_code(dtype))
+        if not table:
+            raise N.NativeError('rows-adjoint-t plugin exports no table for %s' % dtype)
+        hit = (lib, int(table))
+        _ROWS_ADJOINT_T_PLUGINS[(source, dtype)] = hit
+    return hit
 
 
 _COOP_TEMPLATE = """// generated by tfdiffeq_amd.rhs.CustomCoop - do not edit

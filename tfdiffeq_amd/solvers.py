@@ -348,6 +348,27 @@ class _FusedEngine(object):
                                                         self._stream()), 'mi_ode_integrate_rows')
         return out, rows, rc
 
+    def integrate_rows_t(self, rt, y0=None, rows_t_plugin=None):
+        """Per-trajectory step control with per-row times, lengths and tolerances (mi_ode_integrate_rows_t): as integrate_rows.  rt: a
+        rows_times.RowsTimes whose tensors are on this engine's device; rows_t_plugin: (library, table) of a plugin's rows-t plugin."""
+        y0 = self._check_y0(y0)
+        for x, dt in ((rt.t, torch.float64), (rt.lengths, torch.int32), (rt.rtol, torch.float64), (rt.atol, torch.float64)):
+            if x is not None and (x.device != self.device or x.dtype != dt or not x.is_contiguous()):
+                raise ValueError('per-row inputs: contiguous %s tensors on %s are needed' % (dt, self.device))
+        if tuple(rt.t.shape) != (self.batch, rt.T) or any(x is not None and tuple(x.shape) != (self.batch,) for x in (rt.lengths, rt.rtol, rt.atol)):
+            raise ValueError('per-row inputs: t [%d, T] and [%d] lengths / tolerances are needed' % (self.batch, self.batch))
+
+        def ptr(x):
+            return C.c_void_p(x.data_ptr() if x is not None else 0)
+        out = torch.empty((rt.T,) + self.shape, dtype=self.dtype, device=self.device)
+        rows = torch.empty((self.batch, 4), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = N.check(self.lib.mi_ode_integrate_rows_t(self.h, C.c_void_p(rows_t_plugin[1] if rows_t_plugin is not None else 0),
+                                                          C.c_void_p(y0.data_ptr()), ptr(rt.t), rt.T, ptr(rt.lengths), ptr(rt.rtol), ptr(rt.atol),
+                                                          C.c_void_p(out.data_ptr()), C.c_void_p(rows.data_ptr()), C.byref(self.stats),
+                                                          self._stream()), 'mi_ode_integrate_rows_t')
+        return out, rows, rc
+
     def begin(self, t0, y0=None):
         y0 = self._check_y0(y0)
         with torch.cuda.device(self.device):
@@ -837,14 +858,33 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
         self.stats['route'] = route.kind                         # (as decided, whatever the run fell back to)
         return out
 
-    def _integrate_rows(self, route, t):
-        """options['per_trajectory']: k_rows_rowlocal, one launch - there is no other schedule, so nothing here falls back."""
+    def integrate_rows_t(self, rt):
+        """integrate() for per-row times, lengths and tolerances (rows_times.RowsTimes, checked there): k_rows_rowlocal_t."""
+        self.route()                                             # (a refusal is a ValueError of the call, whatever device y0 is on)
+        for y_ in self.y0:
+            N.require_gpu_tensor(y_, 'y0')
+        route = self.route()
+        out = self._integrate_rows(route, None, rt)
+        self.stats['route'] = route.kind
+        return out
+
+    def _integrate_rows(self, route, t, rt=None):
+        """options['per_trajectory']: k_rows_rowlocal, one launch - there is no other schedule, so nothing here falls back.  rt: per-row
+        times, lengths and tolerances in place of t (k_rows_rowlocal_t, likewise)."""
         rhs, y = route.rhs, self.y0[0]
         eng = self._make_engine(route)
-        plugin = rhs.rows_plugin(y.dtype) if rhs.kind == N.RHS_PLUGIN else None
-        times = t.to(torch.float64).numpy()
-        out, rows, bits = eng.integrate_rows(times, y, plugin)
-        self.stats = dict(eng.stats.as_dict(), engine='k_rows_rowlocal: ' + D.ROWS_WHY, per_trajectory=True,
+        if rt is None:
+            plugin = rhs.rows_plugin(y.dtype) if rhs.kind == N.RHS_PLUGIN else None
+            times = t.to(torch.float64).numpy()
+            out, rows, bits = eng.integrate_rows(times, y, plugin)
+            engine = 'k_rows_rowlocal: ' + D.ROWS_WHY
+        else:
+            if y.dim() != 2:
+                raise ValueError("options['per_trajectory'] refused: per-row times, lengths or tolerances need a [batch, dim] state")
+            plugin = rhs.rows_t_plugin(y.dtype) if rhs.kind == N.RHS_PLUGIN else None
+            out, rows, bits = eng.integrate_rows_t(rt, y, plugin)
+            engine = 'k_rows_rowlocal_t: ' + D.ROWS_T_WHY
+        self.stats = dict(eng.stats.as_dict(), engine=engine, per_trajectory=True,
                           rows={'n_attempts': rows[:, 0], 'n_accepted': rows[:, 1], 'nfe': rows[:, 2], 'status': rows[:, 3]})
         if bits:
             bad = torch.nonzero(rows[:, 3]).flatten().tolist()
@@ -852,10 +892,18 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
             # row i is what the call on y0[i:i+1] computes: that call words the assertion (the reference's message, with the row's own dt)
             msg = N.status_message(int(rows[first, 3]))
             row = y.reshape(-1, rhs.dim)[first:first + 1].contiguous()
+            kept = self.rtol, self.atol
             try:
+                if rt is not None:                               # ... on the row's own times, at the row's own tolerances
+                    times = rt.t[first, :int(rt.lengths[first]) if rt.lengths is not None else rt.T].cpu().numpy()
+                    for name, x in (('rtol', rt.rtol), ('atol', rt.atol)):
+                        if x is not None:
+                            setattr(self, name, float(x[first]) if self.pooled_ratio else [float(x[first])])
                 self._make_engine(route, row).integrate(times, row)
             except AssertionError as e:
                 msg = str(e)
+            finally:
+                self.rtol, self.atol = kept
             raise AssertionError('%s [per_trajectory: %d of %d rows failed; rows %s%s, the message is row %d\'s]' % (
                 msg, len(bad), int(rows.shape[0]), ', '.join(str(i) for i in bad[:8]), ', ...' if len(bad) > 8 else '', first))
         return (out,)
