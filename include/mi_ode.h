@@ -276,6 +276,21 @@ int mi_ode_integrate_rows(mi_ode_handle h, const void* rows_plugin, const void* 
 int mi_ode_integrate_rows_t(mi_ode_handle h, const void* rows_t_plugin, const void* y0_dev, const double* t_dev, int32_t T,
                             const int32_t* len_dev, const double* rtol_dev, const double* atol_dev, void* out_dev,
                             int64_t* row_stats_dev, mi_ode_stats* stats, void* stream);
+/* A fixed-grid solve (euler / rk4 on the default grid) with output times and a length of every row's own (csrc/mi_ode_fixed_rows_t.h).
+ * Row i of out_dev is what mi_ode_fixed_grid_integrate returns for y0[i] alone with the times t_dev[i][0 .. len_i - 1], bit for bit;
+ * out_dev[k][i] for k >= len_i is exactly 0 and t_dev[i][len_i ..] is never read.
+ *   h             a fixed-grid handle (adaptive 0, no multistep; the euler or the rk4 3/8 tableau) of a trajectory-per-thread right-hand
+ *                 side, one state tensor on one rank
+ *   fixed_rows_t_plugin   the table mi_ode_fixed_rows_t_plugin_get(dtype) of the plugin's fixed-rows-t shared object returned
+ *                 (csrc/mi_ode_fixed_rows_t_plugin.h) when the handle's right-hand side is a row-local plugin; NULL for the catalogue systems
+ *   t_dev         DEVICE [batch][T] float64, every row strictly increasing over its own length, values already rounded to the state
+ *                 dtype (the caller checks that: nothing of it is read on the host; times that are not give wrong numbers, never an
+ *                 access outside the row)
+ *   len_dev       DEVICE [batch] int32 with values in 1 .. T (clamped to that range by the kernel), or NULL: every row has T times
+ *   out_dev       [T, batch, dim]
+ * One launch and one synchronisation; returns 0 or a negative MI_ODE_E_* (MI_ODE_E_INVALID for null arguments or another handle). */
+int mi_ode_integrate_fixed_rows_t(mi_ode_handle h, const void* fixed_rows_t_plugin, const void* y0_dev, const double* t_dev, int32_t T,
+                                  const int32_t* len_dev, void* out_dev, mi_ode_stats* stats, void* stream);
 /* FixedGridODESolver.integrate(t) with grid = t (solvers.py:82-104); no host synchronisation inside. */
 int mi_ode_fixed_grid_integrate(mi_ode_handle h, const void* y0_dev, const double* t_host, int32_t T,
                                 void* out_dev, mi_ode_stats* stats, void* stream);
@@ -506,6 +521,31 @@ typedef struct mi_ode_discrete_row_desc {
  * (MI_ODE_E_INVALID for a null / inconsistent descriptor or another table in rhs->plugin, MI_ODE_E_NODEVICE without a device). */
 int mi_ode_discrete_row_sweep(const mi_ode_discrete_row_desc* desc, const mi_ode_rhs* rhs, const void* ys_dev, const void* grad_ys_dev,
                               void* grad_y0_out_dev, void* grad_theta_out_dev, mi_ode_stats* stats, void* stream);
+
+/* The same for a solve with times and a length of every row's own (mi_ode_integrate_fixed_rows_t; csrc/mi_ode_discrete_row_t.h): the exact
+ * gradient of every row's own discrete map, all rows and all steps in ONE launch.  grad y0 of row i is what mi_ode_discrete_row_sweep
+ * returns for row i alone with the times t[i][0 .. len_i - 1], bit for bit; grad theta is the sum over the rows in the fixed order of
+ * mi_ode_discrete_row_sweep.  rhs: MI_ODE_RHS_PLUGIN with `plugin` = what a discrete-t plugin's mi_ode_discrete_t_plugin_get(dtype)
+ * returned (csrc/mi_ode_discrete_t_plugin.h).  euler and rk4 (tableaus of 0 and 3 rows). */
+typedef struct mi_ode_discrete_row_t_desc {
+  int32_t dtype;              /* MI_ODE_F32 / MI_ODE_F64 */
+  int32_t n_times;            /* T >= 1: the second axis of the times, the longest row */
+  int64_t batch;
+  int32_t dim;                /* <= 32, the plugin's */
+  int32_t n_params;           /* P <= 1024: trainable elements, the plugin's */
+  int32_t grid;               /* workgroups, 1 .. min(1024, ceil(batch / 256)) */
+  int32_t reserved;
+  mi_ode_tableau tableau;     /* explicit, 0 or 3 rows (1 or 4 stages): beta = a_ij, c_sol = b */
+  const double* t_dev;        /* device [batch][T] float64 (values already rounded to the state dtype); row i is read up to len_i - 1 only */
+  const int32_t* len_dev;     /* device [batch] with values in 1 .. T (clamped to that range by the kernel), or NULL: every row has T times */
+  void* partials_dev;         /* device workspace: grid * P elements of the state dtype */
+  void* ticket_dev;           /* device: one zeroed 32-bit word (left zero again) */
+} mi_ode_discrete_row_t_desc;
+/* ys_dev / grad_ys_dev [T, batch, dim]: grad_ys_dev[k][i] for k >= len_i is never read; grad_y0_out_dev [batch, dim]; grad_theta_out_dev
+ * [P].  Enqueues one launch on `stream`; returns 0 or a negative MI_ODE_E_* as mi_ode_discrete_row_sweep does. */
+int mi_ode_discrete_row_sweep_t(const mi_ode_discrete_row_t_desc* desc, const mi_ode_rhs* rhs, const void* ys_dev, const void* grad_ys_dev,
+                                void* grad_y0_out_dev, void* grad_theta_out_dev, mi_ode_stats* stats, void* stream);
+int64_t mi_ode_discrete_row_t_sizeof(void);               /* sizeof(mi_ode_discrete_row_t_desc), for a binding's layout check */
 
 /* ---- (A-rows-adjoint) gradients of a per-trajectory solve (mi_ode_integrate_rows) for a row-local f with a generated vjp, ONE launch ---- */
 /* The reference's adjoint algorithm (adjoint.py:117-178) applied to every row of the batch ALONE (csrc/mi_ode_rows_adjoint.h): for

@@ -107,6 +107,13 @@ class DiscreteRowDesc(C.Structure):
 DISCRETE_ROW_MAX_PARAMS, DISCRETE_ROW_THREADS, DISCRETE_ROW_MAX_GRID = 1024, 256, 1024
 
 
+class DiscreteRowTDesc(C.Structure):
+    """mi_ode_discrete_row_t_desc: the same with every row's own times and length."""
+    _fields_ = [('dtype', C.c_int32), ('n_times', C.c_int32), ('batch', C.c_int64), ('dim', C.c_int32), ('n_params', C.c_int32),
+                ('grid', C.c_int32), ('reserved', C.c_int32), ('tableau', Tableau),
+                ('t_dev', C.c_void_p), ('len_dev', C.c_void_p), ('partials_dev', C.c_void_p), ('ticket_dev', C.c_void_p)]
+
+
 class AdjointRowsDesc(C.Structure):
     """mi_ode_adjoint_rows_desc: the adjoint of a per-trajectory solve of a lowered row-local callable in one launch."""
     _fields_ = [('dtype', C.c_int32), ('n_times', C.c_int32), ('batch', C.c_int64), ('dim', C.c_int32), ('n_params', C.c_int32),
@@ -213,6 +220,8 @@ _PROTOS = {
                                         C.POINTER(Stats), C.c_void_p]),
     'mi_ode_integrate_rows_t': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_integrate_fixed_rows_t': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                C.POINTER(Stats), C.c_void_p]),
     'mi_ode_fixed_grid_integrate': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p,
                                               C.POINTER(Stats), C.c_void_p]),
     'mi_ode_fixed_grid_integrate_on': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.c_int32,
@@ -261,6 +270,9 @@ _PROTOS = {
     'mi_ode_discrete64_profile': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     'mi_ode_discrete_row_sweep': (C.c_int, [C.POINTER(DiscreteRowDesc), C.POINTER(Rhs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_discrete_row_sweep_t': (C.c_int, [C.POINTER(DiscreteRowTDesc), C.POINTER(Rhs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_discrete_row_t_sizeof': (C.c_int64, []),
     'mi_ode_adjoint_rows': (C.c_int, [C.POINTER(AdjointRowsDesc), C.POINTER(Rhs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(Stats), C.c_void_p]),
     'mi_ode_adjoint_rows_sizeof': (C.c_int64, []),
@@ -370,6 +382,8 @@ def load():
         raise NativeError('struct layout mismatch for AdjointRowsDesc: C %d vs ctypes %d' % (lib.mi_ode_adjoint_rows_sizeof(), C.sizeof(AdjointRowsDesc)))
     if lib.mi_ode_adjoint_rows_t_sizeof() != C.sizeof(AdjointRowsTDesc):
         raise NativeError('struct layout mismatch for AdjointRowsTDesc: C %d vs ctypes %d' % (lib.mi_ode_adjoint_rows_t_sizeof(), C.sizeof(AdjointRowsTDesc)))
+    if lib.mi_ode_discrete_row_t_sizeof() != C.sizeof(DiscreteRowTDesc):
+        raise NativeError('struct layout mismatch for DiscreteRowTDesc: C %d vs ctypes %d' % (lib.mi_ode_discrete_row_t_sizeof(), C.sizeof(DiscreteRowTDesc)))
     _lib = lib
     return lib
 

@@ -539,9 +539,9 @@ class _RowPlan(object):
             self.dim *= int(s_)
 
 
-def _row_plan(func, params, method, y0, build=True):
+def _row_plan(func, params, method, y0, build=True, per_row_t=False):
     """(_RowPlan, '') when the fused row-local sweep takes this call, else (None, why not).  Traces, classifies, generates the vjp and
-    builds the plugin - at the call, not in backward."""
+    builds the plugin - at the call, not in backward.  per_row_t: the discrete-t plugin (per-row times and lengths, _row_sweep_t)."""
     from . import lower as L
     why = _state_refusal(y0, method, 'fused row-local sweep')
     if why:
@@ -585,7 +585,7 @@ def _row_plan(func, params, method, y0, build=True):
         return source, ''
     from . import rhs as R
     try:
-        lib, table = R.discrete_plugin(source, y0.dtype)
+        lib, table = R.discrete_t_plugin(R.discrete_t_source_of(source), y0.dtype) if per_row_t else R.discrete_plugin(source, y0.dtype)
     except N.NativeError as e:
         return None, 'the generated vjp did not compile (%s)' % str(e).split(';')[0]
     prog = L.program_for(tr)
@@ -625,6 +625,106 @@ def _row_sweep(plan, method, t, ys, grad_ys):
                                                           C.byref(stats), N.stream_ptr(dev)), 'mi_ode_discrete_row_sweep')
     del t_dev, work
     return g_y0, g_th, int(stats.n_launches)
+
+
+def _row_sweep_t(plan, method, t_rows, lengths, ys, grad_ys):
+    """_row_sweep over per-row times: t_rows [batch, T] float64 on the device (values rounded to the state dtype, read as given), lengths
+    [batch] int32 there or None - ys / grad_ys: [T, batch, dim], contiguous.  One launch (csrc/mi_ode_discrete_row_t.h)."""
+    from .solvers import _fill_tableau
+    n_pts, batch, dim = (int(v) for v in ys.shape)
+    dev, dtype = ys.device, ys.dtype
+    groups = (batch + N.DISCRETE_ROW_THREADS - 1) // N.DISCRETE_ROW_THREADS
+    grid = min(groups, N.DISCRETE_ROW_MAX_GRID)
+    if int(ROW_GRID) > 0:
+        grid = max(1, min(int(ROW_GRID), grid))
+    P = plan.n_params
+    if tuple(t_rows.shape) != (batch, n_pts) or t_rows.dtype != torch.float64 or not t_rows.is_contiguous() or t_rows.device != dev:
+        raise ValueError('odeint_discrete: per-row times must be a contiguous float64 [batch, T] tensor on the state\'s device')
+    if lengths is not None and (tuple(lengths.shape) != (batch,) or lengths.dtype != torch.int32 or not lengths.is_contiguous() or lengths.device != dev):
+        raise ValueError('odeint_discrete: per-row lengths must be a contiguous int32 [batch] tensor on the state\'s device')
+    d = N.DiscreteRowTDesc()
+    d.dtype, d.n_times, d.batch, d.dim, d.n_params, d.grid = N.dtype_code(dtype), n_pts, batch, dim, P, grid
+    _fill_tableau(d.tableau, TABLEAUS[method], None)
+    words = grid * max(P, 1)
+    work = torch.zeros(words + 2, dtype=dtype, device=dev)   # [grid, P] partials, then the ticket word (zeroed)
+    d.t_dev, d.len_dev = t_rows.data_ptr(), (lengths.data_ptr() if lengths is not None else None)
+    d.partials_dev, d.ticket_dev = work.data_ptr(), work.data_ptr() + words * work.element_size()
+    r = N.Rhs()
+    r.kind, r.sign, r.plugin = N.RHS_PLUGIN, 1.0, plan.table
+    for i, v in enumerate(plan.scalars[:8]):
+        r.scalars[i] = v
+    if plan.pool is not None:
+        r.w[0] = plan.pool.data_ptr()
+    g_y0 = torch.empty(batch, dim, dtype=dtype, device=dev)
+    g_th = torch.empty(max(P, 1), dtype=dtype, device=dev)
+    stats = N.Stats()
+    with torch.cuda.device(dev):
+        N.check(N.load().mi_ode_discrete_row_sweep_t(C.byref(d), C.byref(r), ys.data_ptr(), grad_ys.data_ptr(), g_y0.data_ptr(), g_th.data_ptr(),
+                                                     C.byref(stats), N.stream_ptr(dev)), 'mi_ode_discrete_row_sweep_t')
+    del work
+    return g_y0, g_th, int(stats.n_launches)
+
+
+class _OdeintDiscreteRowsT(torch.autograd.Function):
+    """odeint_discrete with a 2-D `t`: the forward is the fixed_rows.py solve, the backward the one-launch sweep over per-row times."""
+
+    @staticmethod
+    def forward(ctx, func, fwd, method, options, t, plan, prepared, n_steps, n_params, *args):
+        from . import fixed_rows
+        params, y0 = args[:n_params], args[n_params]
+        ctx.method, ctx.params, ctx.plan, ctx.n_steps = method, params, plan, n_steps
+        rt = prepared[1]
+        with torch.no_grad():                            # (the target and the times of the call's planning: nothing is validated twice)
+            ans = fixed_rows.solve(fwd, y0, t, method, options, prepared=prepared)
+        ctx.forward_stats = dict(odeint.last_stats) if isinstance(odeint.last_stats, dict) else {}
+        ctx.t_rows = (-rt.t if rt.decreasing else rt.t).contiguous()      # (read as given: h < 0 for decreasing rows)
+        ctx.lengths = rt.lengths
+        ctx.save_for_backward(ans)
+        return ans
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        ans, = ctx.saved_tensors
+        plan, params = ctx.plan, ctx.params
+        with torch.no_grad():
+            g_y0, theta, n_launches = _row_sweep_t(plan, ctx.method, ctx.t_rows, ctx.lengths, ans.contiguous(), grad_output.contiguous())
+            gp = [None] * len(params)
+            for k, off, n in plan.targets:
+                gp[k] = theta[off:off + n].reshape(params[k].shape).to(params[k].dtype)
+        odeint_discrete.last_backward_stats = {'engine': 'fused row-local sweep (per-row times)', 'n_launches': n_launches, 'n_steps': ctx.n_steps,
+                                               'n_params': plan.n_params, 'why': '', 'method': ctx.method, 'forward': ctx.forward_stats}
+        return (None,) * 9 + tuple(gp) + (g_y0.reshape(ans.shape[1:]),)
+
+
+def _odeint_discrete_rows_t(func, y0, t, method, options, lower, _forward_func):
+    """odeint_discrete for `t` [batch, T] / options['t_lengths'] (fixed_rows.py): planned at the call - the fused row-local sweep over
+    per-row times, or a ValueError with _row_plan's reason; there is no generic sweep over per-row grids."""
+    from . import fixed_rows
+    head = 'odeint_discrete: a 2-D `t` / options[\'t_lengths\']: '
+    if lower is False:
+        raise ValueError(head + 'lower=False asks for the generic (autograd) sweep, and there is none over per-row grids: the only backward is the '
+                         "fused row-local sweep (lower=None, 'auto' or True)")
+    if not isinstance(y0, torch.Tensor):
+        raise ValueError(head + 'a tuple state: row i of `t` belongs to row i of ONE [batch, dim] state tensor')
+    if method not in fixed_rows.D.FIXED_ROWS_T_METHODS:
+        raise ValueError(fixed_rows.REFUSED + fixed_rows.D.fixed_rows_t_refusal(method, None, (y0,), options, check_rhs=False))
+    fwd = func if _forward_func is None else _forward_func
+    grad = torch.is_grad_enabled()
+    if not grad:
+        return odeint(fwd, y0, t, method=method, options=options)
+    with torch.no_grad():                                # (every refusal of the forward, before anything is built)
+        target = fixed_rows.target(fwd, y0.detach(), t, method, dict(options or {}))
+    N.require_gpu_tensor(y0, 'y0')
+    params = _params_of(func, y0, torch.as_tensor(t))
+    plan, why = _row_plan(func, params, method, y0, per_row_t=True)
+    if plan is None:
+        raise ValueError(head + 'the fused row-local sweep, the only backward over per-row grids, does not take this call: ' + why)
+    if y0.dim() != 2 or plan.dim != int(y0.shape[1]):
+        raise ValueError(head + 'the callable lowers to rows of %d elements, the state is %s: row i of `t` must belong to row i of the program'
+                         % (plan.dim, tuple(y0.shape)))
+    rt = fixed_rows.times(y0, t, options)
+    n_steps = (int(rt.lengths.max()) if rt.lengths is not None else rt.T) - 1
+    return _OdeintDiscreteRowsT.apply(func, fwd, method, options, t, plan, (target, rt), n_steps, len(params), *(tuple(params) + (y0,)))
 
 
 def _params_of(func, y0, t):
@@ -879,13 +979,20 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=
     float32 fused mlp sweep, state and all six parameters float64; with own_grid=True through the same recompute, segments included),
     anything else falls to the generic sweep with the reason in last_backward_stats['why']; True - ValueError with that reason, here at
     the call.  The linear and row-local sweeps keep their precedence, and a float32 network is not affected.
+    `t` of shape [batch, T] with y0 [batch, dim] (options['t_lengths'], an int tensor [batch]: how many of a row's times count), euler and rk4:
+    every row on its own time grid (fixed_rows.py) - the forward is that solve, the backward the exact gradient of every row's own discrete
+    map in ONE launch ('fused row-local sweep (per-row times)', csrc/mi_ode_discrete_row_t.h); grad y0[i] is what the call on
+    (y0[i:i+1], t[i, :len_i]) with lower=True gives, the parameter gradients are summed over the rows in a fixed order, the cotangent of
+    the padding is never read.  There lower=None, 'auto' and True all mean that sweep (a ValueError with the reason where it does not take
+    the call), lower=False, linear=True and mlp64=True are ValueErrors, own_grid has nothing to act on (options['step_size'] is refused).
     `odeint_discrete.last_backward_stats`: {'engine': 'fused linear sweep' | 'fused linear sweep (own grid)' | 'fused row-local sweep' |
-    'fused mlp sweep' | 'fused mlp sweep (float64)' | 'generic sweep', 'n_steps',
+    'fused row-local sweep (per-row times)' | 'fused mlp sweep' | 'fused mlp sweep (float64)' | 'generic sweep', 'n_steps',
     'n_launches', 'why'} of the last backward ('why': the reason the fused kernels were not used)."""
     own_grid = OWN_GRID if own_grid is None else own_grid
     if own_grid not in (False, True):
         raise ValueError('odeint_discrete: own_grid must be False or True, not %r' % (own_grid,))
     check_supported(method, options, t, own_grid=own_grid)
+    asked_lower = lower
     lower = LOWER if lower is None else lower
     if lower not in (False, True, 'auto'):
         raise ValueError("odeint_discrete: lower must be False, True or 'auto', not %r" % (lower,))
@@ -895,6 +1002,16 @@ def odeint_discrete(func, y0, t, method='rk4', options=None, lower=None, linear=
     mlp64 = MLP64 if mlp64 is None else mlp64
     if mlp64 not in (False, True, 'auto'):
         raise ValueError("odeint_discrete: mlp64 must be False, True or 'auto', not %r" % (mlp64,))
+    from . import fixed_rows
+    if fixed_rows.wanted(method, t, options):
+        # `t` [batch, T] / options['t_lengths']: the only backward is the fused row-local sweep over per-row times.  lower=None means that
+        # sweep here (not the module default); linear=True / mlp64=True promise an engine that has no per-row form: a ValueError, as
+        # wherever their engine does not take the call ('auto' falls through to the one sweep there is).
+        for name, value in (('linear', linear), ('mlp64', mlp64)):
+            if value is True:
+                raise ValueError('odeint_discrete(%s=True): a 2-D `t` / options[\'t_lengths\'] has one backward, the fused row-local sweep over '
+                                 'per-row times; the fused %s sweep reads one shared grid' % (name, 'linear' if name == 'linear' else 'float64 mlp'))
+        return _odeint_discrete_rows_t(func, y0, t, method, options, asked_lower, _forward_func)
     tensor_input = isinstance(y0, torch.Tensor)
     ys = (y0,) if tensor_input else tuple(y0)
     for y_ in ys:

@@ -180,6 +180,53 @@ def rows_t_refusal(y_shape, t_shape, lengths_shape=None, lengths_is_int=True, rt
     return ''
 
 
+FIXED_ROWS_T_WHY = 'euler / rk4 on every row\'s own time grid (per-row times and lengths), one launch'
+FIXED_ROWS_T_REFUSED = 'a 2-D `t` / options[\'t_lengths\'] with a fixed-grid or Adams method refused: '
+FIXED_ROWS_T_METHODS = ('euler', 'rk4')
+
+
+def fixed_rows_t_refusal(method, dev, y0, options, lowered=None, check_rhs=True):
+    """'' when k_fixed_rowlocal_t (csrc/mi_ode_fixed_rows_t.h) takes a fixed-grid call with a 2-D `t`, else the reason the call is refused
+    with.  Pure: the method's name, the descriptor `dev` behind func (None: a Python callable that was not lowered), the state tuple and
+    the option keys - never the device.  lowered: (kind, dim) of a lowered callable's program; check_rhs False: method, options and state only."""
+    if method not in FIXED_ROWS_T_METHODS:
+        return ('method %r has no one-launch forward kernel a row\'s own time grid could be defined against (bit for bit the batch-of-one '
+                'call): per-row times exist for %s' % (method, ' and '.join(FIXED_ROWS_T_METHODS)))
+    opts = options or {}
+    for key in ('step_size', 'grid_constructor'):
+        if opts.get(key) is not None:
+            return ('options[%r] gives the solver a grid of its own, and per-row grids with interpolated outputs are not built: with a 2-D `t` '
+                    'every row steps on its own times' % key)
+    if float(opts.get('eps', 0.0) or 0.0) != 0.0:
+        return "options['eps'] != 0 shifts the evaluation times off the rows' own grids, which is not built for a 2-D `t`"
+    if opts.get('process_group') is not None:
+        return 'a sharded run (process_group): rows never communicate, so shard the batch yourself and call once per rank'
+    if len(y0) != 1 or not isinstance(y0[0], torch.Tensor):
+        return 'a tuple state: row i of `t` belongs to row i of ONE [batch, dim] state tensor'
+    y = y0[0]
+    if y.dim() != 2 or y.numel() == 0 or y.dtype not in (torch.float32, torch.float64):
+        return 'a state of shape %s, dtype %s: row i of `t` belongs to row i of a non-empty float32 / float64 [batch, dim] state' % (tuple(y.shape), y.dtype)
+    if not check_rhs:
+        return ''
+    if dev is None:
+        return ('a Python callable that was not lowered: only a right-hand side on the trajectory-per-thread kernels can walk every row '
+                'over its own times')
+    if lowered is not None and lowered[0] != 'rowlocal':
+        return rows_family_why("a lowered '%s' program" % lowered[0], lowered[1])
+    if not getattr(dev, 'row_local', False) or not dev.supports(y):
+        return rows_family_why(type(dev).__name__, getattr(dev, 'dim', None))
+    return ''
+
+
+def fixed_rows_t(func, y0, method, options=None):
+    """The fixed-grid solvers with per-row times: k_fixed_rowlocal_t or a ValueError - there is no other schedule."""
+    dev = getattr(func, 'device_rhs', None)
+    why = fixed_rows_t_refusal(method, dev, y0, options)
+    if why:
+        raise ValueError(FIXED_ROWS_T_REFUSED + why)
+    return Route('fused_rows_t', dev, 'k_fixed_rowlocal_t: ' + FIXED_ROWS_T_WHY)
+
+
 ROWS_ADJOINT_WHY = 'per-trajectory adjoint: every row its own augmented solve with per-component control, one launch'
 ROWS_ADJOINT_T_WHY = 'per-trajectory adjoint over per-row times, lengths or tolerances: every row its own augmented solve, one launch'
 ROWS_ADJOINT_METHODS = ('dopri5', 'bosh3')

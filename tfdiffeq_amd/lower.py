@@ -2141,6 +2141,8 @@ class _GeneratedRHS(R.DeviceRHS):
     rows_plugin = R.CustomRowLocal.rows_plugin
     rows_t_source = R.CustomRowLocal.rows_t_source        # (... with per-row times, lengths and tolerances)
     rows_t_plugin = R.CustomRowLocal.rows_t_plugin
+    fixed_rows_t_source = R.CustomRowLocal.fixed_rows_t_source        # (... and euler / rk4 with per-row times and lengths)
+    fixed_rows_t_plugin = R.CustomRowLocal.fixed_rows_t_plugin
 
     def fill(self, rhs, dtype, device):
         keep = super(_GeneratedRHS, self).fill(rhs, dtype, device)

@@ -63,6 +63,11 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
         options, per_row = per_trajectory_option(options)     # (False: the call below, as if the key were absent)
         if per_row:
             return _odeint_per_trajectory(func, y0, t, rtol, atol, method, options)
+    from . import fixed_rows
+    if fixed_rows.wanted(method, t, options):
+        # a fixed-grid method with `t` [batch, T] (options['t_lengths']: how many of a row's times count): every row on its own time grid,
+        # one launch (fixed_rows.py, csrc/mi_ode_fixed_rows_t.h) - or a ValueError with the reason.  A 1-D `t` is the call below, as it was.
+        return fixed_rows.solve(func, y0, t, method, options)
     pre = None
     if _plain_callable_no_grad_state(func, y0):
         # A plain callable over a state that does not require grad: whether it has TRAINABLE inputs of its own is read off its trace - the

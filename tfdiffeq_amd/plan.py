@@ -154,6 +154,9 @@ def plan(func, y0, t=None, rtol=1e-7, atol=1e-9, method=None, options=None, adjo
     opts, per_row = D.per_trajectory_option(opts)
     if per_row:
         return plan_rows(func, y0, rtol, atol, method, opts, t)
+    from . import fixed_rows
+    if fixed_rows.wanted(method, t, opts):
+        return fixed_rows.plan(func, y0, t, method, opts)
     mode = opts.pop('lower', LOWER_DEFAULT)
     tensor_input = isinstance(y0, torch.Tensor)
     ys = (y0,) if tensor_input else tuple(y0)

@@ -517,6 +517,25 @@ class CustomRowLocal(DeviceRHS):
             plugins[dtype] = hit
         return hit
 
+    def fixed_rows_t_source(self, dtype):
+        """The fixed-rows-t plugin of this system (csrc/mi_ode_fixed_rows_t_plugin.h): the same functor behind the fixed-grid kernel with
+        per-row times and lengths."""
+        return fixed_rows_t_source_of(self.source(dtype))
+
+    def fixed_rows_t_plugin(self, dtype):
+        """(library, address of the mi_ode_fixed_rows_t_plugin table) for `dtype`; compiled once, cached by source and header hash."""
+        plugins = self.__dict__.setdefault('_fixed_rows_t_plugins', {})
+        hit = plugins.get(dtype)
+        if hit is None:
+            from . import _plugin_build
+            lib = _plugin_build.build_and_load(self.fixed_rows_t_source(dtype))
+            table = lib.mi_ode_fixed_rows_t_plugin_get(N.dtype_code(dtype))
+            if not table:
+                raise N.NativeError('fixed-rows-t plugin exports no table for %s' % dtype)
+            hit = (lib, int(table))
+            plugins[dtype] = hit
+        return hit
+
 
 _DISCRETE_PLUGINS = {}
 
@@ -576,6 +595,42 @@ def rows_t_source_of(rowlocal_source):
         raise ValueError('not a row-local plugin translation unit: the per-trajectory kernel takes one trajectory per thread')
     src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_rows_t_plugin.h"')
     return src.replace('MI_ODE_DEFINE_ROWLOCAL_PLUGIN(', 'MI_ODE_DEFINE_ROWS_T_PLUGIN(')
+
+
+def fixed_rows_t_source_of(rowlocal_source):
+    """A row-local plugin translation unit (mi_ode_plugin.h) turned into the fixed-rows-t plugin of the same functor (euler / rk4 with
+    per-row times and lengths, csrc/mi_ode_fixed_rows_t_plugin.h)."""
+    if 'MI_ODE_DEFINE_ROWLOCAL_PLUGIN(' not in rowlocal_source:
+        raise ValueError('not a row-local plugin translation unit: the fixed-grid kernel with per-row times takes one trajectory per thread')
+    src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_fixed_rows_t_plugin.h"')
+    return src.replace('MI_ODE_DEFINE_ROWLOCAL_PLUGIN(', 'MI_ODE_DEFINE_FIXED_ROWS_T_PLUGIN(')
+
+
+def discrete_t_source_of(discrete_source):
+    """A discrete plugin translation unit (lower.discrete_source, mi_ode_discrete_plugin.h) turned into the discrete-t plugin of the same
+    functor (the reverse sweep over per-row times and lengths, csrc/mi_ode_discrete_t_plugin.h)."""
+    if 'MI_ODE_DEFINE_DISCRETE_PLUGIN(' not in discrete_source:
+        raise ValueError('not a discrete plugin translation unit: the reverse sweep takes f with its generated vjp')
+    src = discrete_source.replace('#include "mi_ode_discrete_plugin.h"', '#include "mi_ode_discrete_t_plugin.h"')
+    return src.replace('MI_ODE_DEFINE_DISCRETE_PLUGIN(', 'MI_ODE_DEFINE_DISCRETE_T_PLUGIN(')
+
+
+_DISCRETE_T_PLUGINS = {}
+
+
+def discrete_t_plugin(source, dtype):
+    """(library, address of the mi_ode_discrete_row_t_plugin table) of a discrete-t translation unit (discrete_t_source_of); compiled once,
+    cached by source and header hash."""
+    hit = _DISCRETE_T_PLUGINS.get((source, dtype))
+    if hit is None:
+        from . import _plugin_build
+        lib = _plugin_build.build_and_load(source)
+        table = lib.mi_ode_discrete_t_plugin_get(N.dtype_code(dtype))
+        if not table:
+            raise N.NativeError('discrete-t plugin exports no table for %s' % dtype)
+        hit = (lib, int(table))
+        _DISCRETE_T_PLUGINS[(source, dtype)] = hit
+    return hit
 
 
 def rows_adjoint_t_source_of(adjoint_source):

@@ -43,15 +43,16 @@ def _per_row(x, batch, device):
     return torch.as_tensor(x).detach().to(device=device, dtype=torch.float64).contiguous(), None
 
 
-def prepare(y0, t, rtol, atol, options):
+def prepare(y0, t, rtol, atol, options, prefix=_REFUSED):
     """(RowsTimes | None for the shared-t call, options without 't_lengths').  ValueError: a refusal; AssertionError: a row that is not
-    strictly monotone (the reference's text, with the row); TypeError: `t` that is not floating point (misc._check_inputs)."""
+    strictly monotone (the reference's text, with the row); TypeError: `t` that is not floating point (misc._check_inputs).  prefix: what
+    a refusal's message starts with (the fixed-grid route of fixed_rows.py has its own; the default leaves the texts as they are)."""
     opts = dict(options or {})
     wanted, why = shapes(y0, t, rtol, atol, opts)
     if not wanted:
         return None, options
     if why:
-        raise ValueError(_REFUSED + why)
+        raise ValueError(prefix + why)
     lengths = opts.pop('t_lengths', None)
     y = y0[0] if isinstance(y0, (tuple, list)) else y0
     batch, dev = int(y.shape[0]), y.device
@@ -63,7 +64,7 @@ def prepare(y0, t, rtol, atol, options):
         t = t[None, :].expand(batch, t.shape[0])
     T = int(t.shape[1])
     if T < 1:
-        raise ValueError(_REFUSED + '`t` without a time')
+        raise ValueError(prefix + '`t` without a time')
     rt = RowsTimes()
     rt.T = T
     rt.lengths = None if lengths is None else lengths.detach().to(device=dev, dtype=torch.int32).contiguous()
@@ -77,7 +78,7 @@ def prepare(y0, t, rtol, atol, options):
     all_up, all_down, len_ok = (torch.stack([x.all() for x in flags]).tolist() + [True])[:3]       # (the one host read)
     if not len_ok:
         bad = torch.nonzero((rt.lengths < 1) | (rt.lengths > T)).flatten().tolist()
-        raise ValueError(_REFUSED + "options['t_lengths'] must lie in 1 .. T = %d: row %d has %d (%d rows out of range)"
+        raise ValueError(prefix + "options['t_lengths'] must lie in 1 .. T = %d: row %d has %d (%d rows out of range)"
                          % (T, bad[0], int(rt.lengths[bad[0]]), len(bad)))
     if not (all_up or all_down):
         row_up, row_down = up.all(dim=1), down.all(dim=1)
@@ -87,7 +88,7 @@ def prepare(y0, t, rtol, atol, options):
                                  '%d such rows]' % (crooked[0], len(crooked)))      # misc.py:159 (sic)
         first_down = int(torch.nonzero(~row_up).flatten()[0])
         first_up = int(torch.nonzero(~row_down).flatten()[0])
-        raise ValueError(_REFUSED + 'rows of `t` that run in different directions (row %d increases, row %d decreases): the sign of a '
+        raise ValueError(prefix + 'rows of `t` that run in different directions (row %d increases, row %d decreases): the sign of a '
                          'decreasing call goes to the right-hand side once, for every row - call once per direction' % (first_up, first_down))
     rt.decreasing = not all_up
     rt.t = (-t if rt.decreasing else t).contiguous()

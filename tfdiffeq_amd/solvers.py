@@ -369,6 +369,25 @@ class _FusedEngine(object):
                                                           self._stream()), 'mi_ode_integrate_rows_t')
         return out, rows, rc
 
+    def integrate_fixed_rows_t(self, rt, y0=None, plugin=None):
+        """euler / rk4 with per-row times and lengths (mi_ode_integrate_fixed_rows_t): the solution [T, batch, dim].  rt: a
+        rows_times.RowsTimes whose tensors are on this engine's device, times already rounded to the state dtype; plugin: (library,
+        table) of a plugin right-hand side's fixed-rows-t plugin."""
+        y0 = self._check_y0(y0)
+        for x, dt in ((rt.t, torch.float64), (rt.lengths, torch.int32)):
+            if x is not None and (x.device != self.device or x.dtype != dt or not x.is_contiguous()):
+                raise ValueError('per-row inputs: contiguous %s tensors on %s are needed' % (dt, self.device))
+        if len(self.shape) != 2 or tuple(rt.t.shape) != (self.batch, rt.T) or (rt.lengths is not None and tuple(rt.lengths.shape) != (self.batch,)):
+            raise ValueError('per-row inputs: a [%d, dim] state, t [%d, T] and [%d] lengths are needed' % (self.batch, self.batch, self.batch))
+        out = torch.empty((rt.T,) + self.shape, dtype=self.dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.mi_ode_integrate_fixed_rows_t(self.h, C.c_void_p(plugin[1] if plugin is not None else 0), C.c_void_p(y0.data_ptr()),
+                                                           C.c_void_p(rt.t.data_ptr()), rt.T,
+                                                           C.c_void_p(rt.lengths.data_ptr() if rt.lengths is not None else 0),
+                                                           C.c_void_p(out.data_ptr()), C.byref(self.stats), self._stream()),
+                    'mi_ode_integrate_fixed_rows_t')
+        return out
+
     def begin(self, t0, y0=None):
         y0 = self._check_y0(y0)
         with torch.cuda.device(self.device):
@@ -633,6 +652,24 @@ class FixedGridODESolver(object):
             out = self._integrate_planes(None, t)
         self.stats['route'] = route.kind
         return out
+
+    def integrate_rows_t(self, rt):
+        """integrate() for per-row times and lengths (rows_times.RowsTimes, checked there; fixed_rows.py): k_fixed_rowlocal_t, one launch -
+        there is no other schedule, so nothing here falls back."""
+        opts = {'eps': self.eps, 'process_group': self._pg}
+        if not getattr(self, '_default_grid', False):
+            opts['step_size'] = True
+        route = D.fixed_rows_t(self.func, self.y0, type(self).__name__.lower(), opts)     # (a refusal is a ValueError, whatever device y0 is on)
+        for y_ in self.y0:
+            N.require_gpu_tensor(y_, 'y0')
+        rhs, y = route.rhs, self.y0[0]
+        key = ('fixed', rhs.cache_key(y.dtype, y.device), tuple(y.shape), y.dtype, str(y.device),
+               _tableau_key(self._fused_tableau, None), self._fusion)
+        eng = _cached_engine(key, lambda: _FusedEngine(rhs, y, False, self._fused_tableau, fusion=self._fusion))
+        plugin = rhs.fixed_rows_t_plugin(y.dtype) if rhs.kind == N.RHS_PLUGIN else None
+        out = eng.integrate_fixed_rows_t(rt, y, plugin)
+        self.stats = dict(eng.stats.as_dict(), engine=route.why, route=route.kind)
+        return (out,)
 
     def _own_grid(self):
         return not (getattr(self, '_default_grid', False) and self.eps == 0.0)
