@@ -87,7 +87,9 @@ extern "C" int mi_ode_adjoint_create(const mi_ode_adjoint_desc* desc, mi_ode_adj
   int cus = 0;
   const int rc = handoff_device(h->fn, 3, c.block, c.lds, &cus, "fused adjoint");
   if (rc != 0) { mi_ode_adjoint_destroy(h); return rc; }
-  c.grid = handoff_cap_grid(h->ntiles, cus);
+  int g = handoff_cap_grid(h->ntiles, cus);
+  if (const char* eg = getenv("MI_ODE_ADJOINT_GRID")) { const int v = atoi(eg); if (v >= 1 && v <= g) g = v; }   // tests: a smaller grid (co-residency holds); a value outside [1, the natural grid] is ignored
+  c.grid = g;
   h->SL = (h->P + c.grid - 1) / c.grid;
   const size_t n = (size_t)desc->batch * (size_t)d;
   size_t slot_floats = (size_t)32 * (2 * (size_t)h->dp + 4 * (size_t)h->hp);
