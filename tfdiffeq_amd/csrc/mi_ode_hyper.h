@@ -127,6 +127,8 @@ __device__ __forceinline__ const T* hyper_g(const HyperArgs& A, const T* wb, T* 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const T v = hyper_act<T>(act, acc[r] + bias, a);
+        // (the select is redundant for finite rows: the next layer's weight rows out .. Kp - 1 are zero in the pack, so whatever a padded
+        // column holds - act(0), e.g. log 2 under Softplus - is multiplied by 0; only a non-finite row's padded columns differ, and its live columns are non-finite already)
         dst[M::row(lane, r) * kHypLd + col] = col < out ? v : (T)0;
       }
     }

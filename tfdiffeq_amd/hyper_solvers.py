@@ -10,7 +10,8 @@ Two engines; `<solver>.last_stats` says which one ran a call and why:
           kernels' functor, g's layers on the matrix cores.  Taken when the state is a 2-D float32 / float64 CUDA tensor, f is a row-local
           device system (rhs.Lorenz, rhs.LotkaVolterra, the 2 x 2 rhs.Linear / rhs.CubicLinear, rhs.CustomRowLocal) or a Python callable
           that tfdiffeq_amd.lower maps to a row-local program, g is an nn.Sequential that `describe_g` accepts, and no result would
-          require grad.
+          require grad.  `last_stats['n_launches']` is 1 while g's weights fit in LDS beside the two activation tiles, and 2 (the weight
+          pack into the workspace, then the kernel) for a larger g.
   eager   everything else: the reference's loop in torch operations on the GPU - differentiable, the training path.
 CPU tensors are refused (NativeError), as on every path of this package.
 """
