@@ -844,6 +844,44 @@ typedef struct mi_ode_hyper {
  * workspace first), or a negative MI_ODE_E_*. */
 int mi_ode_hyper_run(const mi_ode_hyper* desc, void* stream);
 
+/* ---- (D') the gradient of a hypersolver call, one launch (csrc/mi_ode_hyper_grad.h) ------------------------------------------
+ * TRAJECTORY: from the forward's output ys [T, batch, dim] and the gradient grad_out [T, batch, dim] of the loss with respect to it,
+ * the reverse sweep over all steps and rows: grad_y [batch, dim] (nullable) and the gradient of every parameter of g whose
+ * grad_w / grad_b / grad_alpha pointer is not null (torch's layouts: [out, in], [out], [n_alpha]).  G_RESIDUALS: ys is the base
+ * trajectory, parameter gradients only.  f: MI_ODE_RHS_PLUGIN with `plugin` = what a hyper-grad plugin's
+ * mi_ode_hyper_grad_plugin_get(dtype) returned (csrc/mi_ode_hyper_grad_plugin.h: f with a generated vjp), sign +1.
+ * workspace: mi_ode_hyper_grad_workspace_bytes(desc) bytes, contents arbitrary (the per-workgroup parameter partials [grid, P] and,
+ * when g's two weight images do not fit in LDS beside the activation tiles, the images); ticket: a 4-byte word that is zero. */
+#define MI_ODE_HYPER_GRAD_MAX_GRID 256
+typedef struct mi_ode_hyper_grad {
+  int32_t dtype;              /* enum mi_ode_dtype */
+  int32_t method;             /* enum mi_ode_hyper_method */
+  int32_t mode;               /* MI_ODE_HYPER_TRAJECTORY or MI_ODE_HYPER_G_RESIDUALS */
+  int32_t n_layers;
+  int64_t batch, dim;
+  int32_t T;                  /* time points, >= 2 */
+  int32_t grid;               /* workgroups: 1 .. min(tiles of 16 rows, MI_ODE_HYPER_GRAD_MAX_GRID) */
+  const void* t;              /* device [T], state dtype */
+  const void* ys;             /* device [T, batch, dim] */
+  const void* grad_out;       /* device [T, batch, dim] */
+  void* grad_y;               /* device [batch, dim], nullable */
+  void* workspace;
+  void* ticket;
+  mi_ode_rhs rhs;             /* f */
+  mi_ode_hyper_layer layers[MI_ODE_HYPER_MAX_LAYERS];
+  void* grad_w[MI_ODE_HYPER_MAX_LAYERS];
+  void* grad_b[MI_ODE_HYPER_MAX_LAYERS];
+  void* grad_alpha[MI_ODE_HYPER_MAX_LAYERS];
+} mi_ode_hyper_grad;
+/* Enqueues the call on `stream`.  Returns the number of kernel launches it enqueued (1, or 2 when the weight images are packed to
+ * the workspace first), or a negative MI_ODE_E_*. */
+int mi_ode_hyper_grad_run(const mi_ode_hyper_grad* desc, void* stream);
+/* Bytes of `workspace` for this descriptor (dtype, grid, n_layers and the layers' widths are read), or a negative MI_ODE_E_*. */
+int64_t mi_ode_hyper_grad_workspace_bytes(const mi_ode_hyper_grad* desc);
+/* Bytes of LDS the gradient kernel needs for g's activation tiles alone (the size limit of the fused gradient), or negative. */
+int64_t mi_ode_hyper_grad_tile_bytes(const mi_ode_hyper_grad* desc);
+int mi_ode_hyper_grad_sizeof(void);
+
 /* ---- (E) convolutional ODE function (tfdiffeq/models/conv_odenet.py: Conv2dODEFunc) -----------------------------------------
  * f(t, y) = conv3(act(conv2(act(conv1(y))))) on NCHW images: conv1 1x1 C -> F, conv2 3x3 zero-padded "same" F -> F, conv3 1x1
  * F -> C, all with biases; time dependent: every conv sees concat([t, x]) along the channels (time is input channel 0, zero padded

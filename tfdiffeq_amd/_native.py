@@ -180,6 +180,21 @@ class HyperDesc(C.Structure):
                 ('rhs', Rhs), ('layers', HyperLayer * HYPER_MAX_LAYERS)]
 
 
+HYPER_GRAD_MAX_GRID = 256
+HYPER_GRAD_LDS_BYTES = 160 * 1024
+
+
+class HyperGradDesc(C.Structure):
+    """mi_ode_hyper_grad: the gradient of a hypersolver call in one launch (include/mi_ode.h section D')."""
+    _fields_ = [('dtype', C.c_int32), ('method', C.c_int32), ('mode', C.c_int32), ('n_layers', C.c_int32),
+                ('batch', C.c_int64), ('dim', C.c_int64), ('T', C.c_int32), ('grid', C.c_int32),
+                ('t', C.c_void_p), ('ys', C.c_void_p), ('grad_out', C.c_void_p), ('grad_y', C.c_void_p),
+                ('workspace', C.c_void_p), ('ticket', C.c_void_p),
+                ('rhs', Rhs), ('layers', HyperLayer * HYPER_MAX_LAYERS),
+                ('grad_w', C.c_void_p * HYPER_MAX_LAYERS), ('grad_b', C.c_void_p * HYPER_MAX_LAYERS),
+                ('grad_alpha', C.c_void_p * HYPER_MAX_LAYERS)]
+
+
 CONV_MAX_C, CONV_MAX_F = 16, 128
 CONV_ACT_RELU, CONV_ACT_SOFTPLUS, CONV_ACT_TANH = 0, 1, 2
 
@@ -326,6 +341,10 @@ _PROTOS = {
     'mi_ode_adams_update_phi': (C.c_int, [C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_double),
                                           C.POINTER(C.c_void_p), C.c_void_p]),
     'mi_ode_hyper_run': (C.c_int, [C.POINTER(HyperDesc), C.c_void_p]),
+    'mi_ode_hyper_grad_run': (C.c_int, [C.POINTER(HyperGradDesc), C.c_void_p]),
+    'mi_ode_hyper_grad_workspace_bytes': (C.c_int64, [C.POINTER(HyperGradDesc)]),
+    'mi_ode_hyper_grad_tile_bytes': (C.c_int64, [C.POINTER(HyperGradDesc)]),
+    'mi_ode_hyper_grad_sizeof': (C.c_int32, []),
     'mi_ode_conv_stage': (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_double), C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mi_ode_interp_eval': (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
@@ -384,6 +403,8 @@ def load():
         raise NativeError('struct layout mismatch for AdjointRowsTDesc: C %d vs ctypes %d' % (lib.mi_ode_adjoint_rows_t_sizeof(), C.sizeof(AdjointRowsTDesc)))
     if lib.mi_ode_discrete_row_t_sizeof() != C.sizeof(DiscreteRowTDesc):
         raise NativeError('struct layout mismatch for DiscreteRowTDesc: C %d vs ctypes %d' % (lib.mi_ode_discrete_row_t_sizeof(), C.sizeof(DiscreteRowTDesc)))
+    if lib.mi_ode_hyper_grad_sizeof() != C.sizeof(HyperGradDesc):
+        raise NativeError('struct layout mismatch for HyperGradDesc: C %d vs ctypes %d' % (lib.mi_ode_hyper_grad_sizeof(), C.sizeof(HyperGradDesc)))
     _lib = lib
     return lib
 

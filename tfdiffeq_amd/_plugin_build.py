@@ -118,7 +118,7 @@ def build_and_load(source):
         lib = C.CDLL(path)
         for name in ('mi_ode_plugin_get', 'mi_ode_hyper_plugin_get', 'mi_ode_discrete_plugin_get', 'mi_ode_rows_plugin_get',
                      'mi_ode_rows_adjoint_plugin_get', 'mi_ode_rows_t_plugin_get', 'mi_ode_rows_adjoint_t_plugin_get',
-                     'mi_ode_fixed_rows_t_plugin_get', 'mi_ode_discrete_t_plugin_get'):     # (one per kind of plugin)
+                     'mi_ode_fixed_rows_t_plugin_get', 'mi_ode_discrete_t_plugin_get', 'mi_ode_hyper_grad_plugin_get'):     # (one per kind of plugin)
             if hasattr(lib, name):
                 getattr(lib, name).restype = C.c_void_p
                 getattr(lib, name).argtypes = [C.c_int]

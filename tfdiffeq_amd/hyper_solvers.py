@@ -14,6 +14,15 @@ Two engines; `<solver>.last_stats` says which one ran a call and why:
           pack into the workspace, then the kernel) for a larger g.
   eager   everything else: the reference's loop in torch operations on the GPU - differentiable, the training path.
 CPU tensors are refused (NativeError), as on every path of this package.
+
+Training on the fused engine is opt-in: options={'grad': False | 'auto' | True} on the constructor (module default FUSED_GRAD = False).
+With 'auto' / True a `trajectory` or `_hypersolver_residuals` call in which something requires grad runs the SAME forward kernel inside
+a torch.autograd.Function whose backward is ONE launch for all steps and rows (csrc/mi_ode_hyper_grad.h; two when g's weight images do
+not fit in LDS): the gradient with respect to g's parameters and, for a trajectory, y.  `describe_grad` is the box, a pure host
+function: f a Python callable the tracer lowers to a row-local program without trainable tensors, or rhs.Lorenz / rhs.LotkaVolterra
+(differentiated through their traced equivalents); g whatever `describe_g` accepts whose activation tiles fit in LDS.  Outside the box
+'auto' trains on the eager engine with the limit in last_stats['why']; True raises ValueError with it.  `last_backward_stats` is set by
+the backward.
 """
 import ctypes
 import importlib
@@ -26,6 +35,9 @@ from . import rhs as R
 
 MAX_LAYERS = N.HYPER_MAX_LAYERS
 MAX_WIDTH = 128
+FUSED_GRAD = False               # the default of options['grad']: False (training on the eager engine), 'auto' or True
+GRAD_GRID = 0                    # cap of the gradient kernel's grid; 0: GRAD_DEFAULT_GRID.  The [grid, P] partials stay small
+GRAD_DEFAULT_GRID = 128
 
 _ACTS = {nn.ReLU: N.HYPER_ACT_RELU, nn.LeakyReLU: N.HYPER_ACT_LEAKY_RELU, nn.PReLU: N.HYPER_ACT_PRELU, nn.Tanh: N.HYPER_ACT_TANH,
          nn.Softplus: N.HYPER_ACT_SOFTPLUS}
@@ -86,9 +98,178 @@ def _describe_f(f):
     return {'kind': 'callable', 'name': getattr(f, '__name__', type(f).__name__)}
 
 
+def grad_tile_bytes(table, dtype):
+    """LDS bytes of the gradient kernel's activation tiles for a `describe_g` table: the input [16][Kp + 1] and the pre-activation
+    [16][Np + 1] of every layer and one cotangent tile [16][widest + 1] (csrc/mi_ode_hyper_grad.h: hyper_grad_layout)."""
+    r16 = lambda n: (n + 15) // 16 * 16                                                              # noqa: E731
+    elems, widest = 0, 16
+    for lin, _, _ in table['layers']:
+        kp, np_ = r16(lin.in_features), r16(lin.out_features)
+        elems += 16 * (kp + 1) + 16 * (np_ + 1)
+        widest = max(widest, kp, np_)
+    elems += 16 * (widest + 1)
+    return (elems + 1) // 2 * 2 * (8 if dtype == torch.float64 else 4) + 16
+
+
+def _g_params(table):
+    """g's parameters in layer order and, per layer, the indices (weight, bias | None, PReLU weight | None) into that list."""
+    params, index = [], []
+    for lin, _, act in table['layers']:
+        row = [len(params), None, None]
+        params.append(lin.weight)
+        if lin.bias is not None:
+            row[1] = len(params)
+            params.append(lin.bias)
+        if isinstance(act, nn.PReLU):
+            row[2] = len(params)
+            params.append(act.weight)
+        index.append(tuple(row))
+    return params, index
+
+
+def describe_grad(f, g, mode, t_span, y, lower_mode='auto'):
+    """The box of the fused gradient, a pure host function (CPU tensors are fine, nothing is compiled or launched): (plan, None) when the
+    one-launch backward can differentiate this call, else (None, the limit that was hit).  mode: N.HYPER_TRAJECTORY (y: the state
+    [batch, dim]) or N.HYPER_G_RESIDUALS (y: the base trajectory [T, batch, dim]).
+    plan: {'source': the hyper-grad plugin's translation unit, 'g': describe_g's table, 'params', 'index': _g_params, 'low': the lowered f,
+    'f_desc', 'tile_bytes'}."""
+    if mode not in (N.HYPER_TRAJECTORY, N.HYPER_G_RESIDUALS):
+        return None, 'residual_trajectory does not evaluate g: there is nothing to train'
+    want = 2 if mode == N.HYPER_TRAJECTORY else 3
+    if not isinstance(y, torch.Tensor) or y.dim() != want or y.dtype not in (torch.float32, torch.float64) or y.numel() == 0:
+        return None, 'the state is not a non-empty %d-D float32 / float64 tensor' % want
+    t_span = torch.as_tensor(t_span)
+    if t_span.dim() != 1 or t_span.shape[0] < 2 or (mode != N.HYPER_TRAJECTORY and t_span.shape[0] != y.shape[0]):
+        return None, 't_span must hold >= 2 times (one per row of the base trajectory)'
+    if t_span.requires_grad:
+        return None, 't_span requires grad (the fused gradient is with respect to g and y)'
+    if mode == N.HYPER_G_RESIDUALS and y.requires_grad:
+        return None, 'the base trajectory requires grad (the fused gradient of _hypersolver_residuals is with respect to g only)'
+    state = (y if mode == N.HYPER_TRAJECTORY else y[0]).detach()
+    dim = int(state.shape[-1])
+    table, why = describe_g(g, dim)
+    if table is None:
+        return None, why
+    params, index = _g_params(table)
+    if any(p.device != y.device or p.dtype != y.dtype or not p.is_contiguous() for p in params):
+        return None, "g's parameters are not contiguous %s tensors on %s (the state's)" % (y.dtype, y.device)
+    tile = grad_tile_bytes(table, y.dtype)
+    if tile > N.HYPER_GRAD_LDS_BYTES:
+        return None, "g is beyond the size limit of the fused gradient: the input and the pre-activation of every layer for a tile of 16 " \
+                     "rows take %d bytes of LDS, the limit is %d" % (tile, N.HYPER_GRAD_LDS_BYTES)
+    f_desc = _describe_f(f)
+    if isinstance(f, R.DeviceRHS):
+        if type(f) not in (R.Lorenz, R.LotkaVolterra):
+            return None, '%s has no vjp for the fused gradient (rhs.Lorenz, rhs.LotkaVolterra and lowered Python callables have)' % type(f).__name__
+        if f.sign != 1.0:
+            return None, 'f runs on a reversed time axis (sign %g)' % f.sign
+        if f.dim != dim:
+            return None, '%s is not a system of the state width %d' % (type(f).__name__, dim)
+        func = f.forward                                 # (the traced equivalent: the same formulas, with a generated vjp)
+    elif callable(f):
+        if lower_mode is False or lower_mode == 'off':
+            return None, 'f is a Python callable and lowering is off'
+        if isinstance(f, nn.Module) and any(p.requires_grad for p in f.parameters()):
+            return None, 'f closes over trainable tensors (its own parameters): the fused gradient is with respect to g and y'
+        func = f
+    else:
+        return None, 'f is not callable'
+    from . import lower as L
+    try:
+        low = L.lower(func, state)
+        if low.kind != 'rowlocal' or tuple(low.state_shape) != tuple(state.shape):
+            raise L.TraceError('the callable lowers to a %s program, not a row-local one' % low.kind)
+        if L.vjp_params(low.trace)[1] or any(e_['t'].requires_grad for e_ in low.trace.tensors if isinstance(e_.get('t'), torch.Tensor)):
+            return None, 'f closes over trainable tensors: the fused gradient is with respect to g and y'
+        source = R.hyper_grad_source_of(L.discrete_source(low.trace))
+    except Exception as e:
+        return None, 'f was not lowered with a vjp: %s' % e
+    if not isinstance(f, R.DeviceRHS):
+        f_desc = dict(low.describe(), lowered=True)
+    return {'source': source, 'g': table, 'params': params, 'index': index, 'low': low, 'f_desc': f_desc, 'tile_bytes': tile}, None
+
+
+class _FusedGrad(torch.autograd.Function):
+    """The forward kernel as it is; the backward is the one launch of csrc/mi_ode_hyper_grad.h."""
+
+    @staticmethod
+    def forward(ctx, solver, mode, t_span, y, plan, gplan, *params):
+        out, n = solver._fused(mode, t_span, y, plan)
+        ctx.solver, ctx.mode, ctx.gplan = solver, mode, gplan
+        solver.last_stats = {'engine': 'fused', 'why': 'fused: one launch', 'n_launches': n, 'f': plan['f_desc'], 'g': plan['g']['text'],
+                             'method': type(solver).__name__, 'grad': 'fused'}
+        ctx.table = R.hyper_grad_plugin(gplan['source'], y.dtype)          # (compiled at the call, not in backward)
+        low = gplan['low']
+        ctx.scalars = list(low.rhs.params)
+        ctx.pool = None if low.rhs.pool is None else low.rhs.pool.clone()  # (the program's pool is shared: the next call overwrites it)
+        ctx.y_grad = mode == N.HYPER_TRAJECTORY and y.requires_grad
+        ctx.p_grad = [p.requires_grad for p in params]
+        ctx.save_for_backward(t_span, out if mode == N.HYPER_TRAJECTORY else y, *params)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        saved = ctx.saved_tensors                        # (an in-place change of a parameter since the forward raises here)
+        t_span, ys, params = saved[0], saved[1].detach().contiguous(), saved[2:]
+        solver, gplan, mode = ctx.solver, ctx.gplan, ctx.mode
+        dtype, device = ys.dtype, ys.device
+        T, B, dim = (int(s_) for s_ in ys.shape)
+        G = G.to(dtype).contiguous()
+        tc = t_span.detach().contiguous()
+        d = N.HyperGradDesc()
+        d.dtype, d.method, d.mode = N.dtype_code(dtype), solver._method if mode == N.HYPER_TRAJECTORY else N.HYPER_EULER, mode
+        d.batch, d.dim, d.T = B, dim, T
+        work = B if mode == N.HYPER_TRAJECTORY else T * B
+        cap = int(GRAD_GRID) if int(GRAD_GRID) > 0 else GRAD_DEFAULT_GRID
+        grid = max(1, min((work + 15) // 16, cap, N.HYPER_GRAD_MAX_GRID))
+        d.grid = grid
+        d.t, d.ys, d.grad_out = tc.data_ptr(), ys.data_ptr(), G.data_ptr()
+        gy = torch.empty((B, dim), dtype=dtype, device=device) if ctx.y_grad else None
+        d.grad_y = gy.data_ptr() if gy is not None else None
+        sizes = [p.numel() if need else 0 for p, need in zip(params, ctx.p_grad)]
+        flat = torch.empty(max(sum(sizes), 1), dtype=dtype, device=device)
+        grads, off = [], 0
+        for p, n_ in zip(params, sizes):
+            grads.append(flat[off:off + n_].view(p.shape) if n_ else None)
+            off += n_
+        layers = gplan['g']['layers']
+        d.n_layers = len(layers)
+        for j, ((lin, act, m), (iw, ib, ia)) in enumerate(zip(layers, gplan['index'])):
+            L_ = d.layers[j]
+            L_.in_, L_.out, L_.act = lin.in_features, lin.out_features, act
+            L_.w = params[iw].data_ptr()
+            L_.b = params[ib].data_ptr() if ib is not None else None
+            if ia is not None:
+                L_.alpha, L_.n_alpha = params[ia].data_ptr(), m.num_parameters
+            elif isinstance(m, nn.LeakyReLU):
+                L_.slope = float(m.negative_slope)
+            d.grad_w[j] = grads[iw].data_ptr() if grads[iw] is not None else None
+            d.grad_b[j] = grads[ib].data_ptr() if ib is not None and grads[ib] is not None else None
+            d.grad_alpha[j] = grads[ia].data_ptr() if ia is not None and grads[ia] is not None else None
+        d.rhs.kind, d.rhs.sign, d.rhs.plugin = N.RHS_PLUGIN, 1.0, ctx.table[1]
+        for i, v in enumerate(ctx.scalars[:8]):
+            d.rhs.scalars[i] = v
+        if ctx.pool is not None:
+            d.rhs.w[0] = ctx.pool.data_ptr()
+        lib = N.load()
+        nbytes = N.check(lib.mi_ode_hyper_grad_workspace_bytes(ctypes.byref(d)), 'mi_ode_hyper_grad_workspace_bytes')
+        work_buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+        ticket = torch.zeros(4, dtype=torch.int32, device=device)
+        d.workspace, d.ticket = work_buf.data_ptr(), ticket.data_ptr()
+        with torch.cuda.device(device):
+            rc = lib.mi_ode_hyper_grad_run(ctypes.byref(d), N.stream_ptr(device))
+        N.check(rc, 'mi_ode_hyper_grad_run')
+        solver.last_backward_stats = {'engine': 'fused', 'n_launches': int(rc), 'grid': grid, 'why': 'fused: one launch for all steps and rows',
+                                      'method': type(solver).__name__}
+        del work_buf, ticket, G, tc                      # (stream-ordered: the caching allocator reuses the memory after the kernel)
+        return (None, None, None, gy, None, None) + tuple(grads)
+
+
 class AbstractHyperSolver(nn.Module):
     """base.py: `f` the ODE function, `g` the network that approximates the truncation error of the base method.
-    options: {'lower': True | False | 'auto'} - trace a Python `f` onto a generated row-local kernel ('auto': odeint's LOWER_DEFAULT)."""
+    options: {'lower': True | False | 'auto'} - trace a Python `f` onto a generated row-local kernel ('auto': odeint's LOWER_DEFAULT);
+    {'grad': False | 'auto' | True} - train on the fused engine (default FUSED_GRAD; see the module's docstring)."""
     _method = None
 
     def __init__(self, func, hyper_solver, options=None):
@@ -96,7 +277,10 @@ class AbstractHyperSolver(nn.Module):
         self.f = func
         self.g = hyper_solver
         self.options = dict(options or {})
+        if self.options.get('grad', False) not in (False, 'auto', True):
+            raise ValueError("options['grad'] is False, 'auto' or True, not %r" % (self.options['grad'],))
         self.last_stats = {}
+        self.last_backward_stats = {}
 
     def forward(self, t, y, dy):
         """g(cat([y, dy, t * ones(B, 1)], dim=1)) (base.py:27-41)."""
@@ -118,6 +302,17 @@ class AbstractHyperSolver(nn.Module):
     def _call(self, mode, t_span, y):
         N.require_gpu_tensor(y, 'y' if mode == N.HYPER_TRAJECTORY else 'base_traj')
         t_span = torch.as_tensor(t_span).to(device=y.device, dtype=y.dtype)
+        grad_opt = self.options.get('grad', FUSED_GRAD)
+        if grad_opt is not False and self._needs_grad(t_span, y):
+            out, why = self._call_fused_grad(mode, t_span, y)
+            if out is not None:
+                return out
+            if grad_opt is True:
+                raise ValueError("hypersolver(options={'grad': True}): the fused gradient does not take this call: %s" % why)
+            out = self._eager(mode, t_span, y)
+            self.last_stats = {'engine': 'eager', 'why': why, 'n_launches': None, 'f': _describe_f(self.f), 'g': self._g_text(y),
+                               'method': type(self).__name__}
+            return out
         plan, why = self._plan(mode, t_span, y)
         if plan is None:
             out = self._eager(mode, t_span, y)
@@ -139,6 +334,24 @@ class AbstractHyperSolver(nn.Module):
         if mode == 'auto':
             mode = importlib.import_module(__package__ + '.odeint').LOWER_DEFAULT
         return mode
+
+    def _needs_grad(self, t_span, y):
+        return torch.is_grad_enabled() and (y.requires_grad or t_span.requires_grad or any(p.requires_grad for p in self.g.parameters()) or
+                                            (isinstance(self.f, nn.Module) and any(p.requires_grad for p in self.f.parameters())))
+
+    def _call_fused_grad(self, mode, t_span, y):
+        """(result, why) of a call that requires grad on the fused engine, or (None, the limit of the box that was hit)."""
+        if isinstance(self.f, nn.Module) and any(p.requires_grad for p in self.f.parameters()):
+            return None, 'f closes over trainable tensors (its own parameters): the fused gradient is with respect to g and y'
+        gplan, why = describe_grad(self.f, self.g, mode, t_span, y, self._lower_mode())
+        if gplan is None:
+            return None, why
+        with torch.no_grad():
+            plan, why = self._plan(mode, t_span, y)
+        if plan is None:
+            return None, why
+        out = _FusedGrad.apply(self, mode, t_span, y, plan, gplan, *gplan['params'])
+        return out, None
 
     def _plan(self, mode, t_span, y):
         """(plan, why) for the fused engine, or (None, why not)."""
@@ -320,3 +533,16 @@ def hyper_sources(f, y0, dtype=None):
         return [f.hyper_source(dtype or y0.dtype)] if hasattr(f, 'hyper_source') and f.kind == N.RHS_PLUGIN else []
     from . import lower as L
     return [R.hyper_source_of(s) for s in L.sources_for(f, y0)]
+
+
+def hyper_grad_sources(f, y0, dtype=None):
+    """The hyper-grad plugin source a fused backward with this f and state would compile (build-time prebuilding; [] outside the box)."""
+    from . import lower as L
+    state = y0.to(dtype) if dtype is not None else y0
+    func = f.forward if type(f) in (R.Lorenz, R.LotkaVolterra) else f
+    if isinstance(func, R.DeviceRHS) or not callable(func):
+        return []
+    tr = L.trace(func, state.detach())
+    if L.program_for(tr).kind != 'rowlocal' or L.vjp_params(tr)[1]:
+        return []
+    return [R.hyper_grad_source_of(L.discrete_source(tr))]

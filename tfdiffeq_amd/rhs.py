@@ -580,6 +580,33 @@ def hyper_source_of(rowlocal_source):
     return src.replace('MI_ODE_DEFINE_ROWLOCAL_PLUGIN(', 'MI_ODE_DEFINE_HYPER_PLUGIN(')
 
 
+def hyper_grad_source_of(discrete_source):
+    """A discrete plugin translation unit (lower.discrete_source, mi_ode_discrete_plugin.h: f with its generated vjp) turned into the
+    hyper-grad plugin of the same functor (the one-launch gradient of a hypersolver call, csrc/mi_ode_hyper_grad_plugin.h)."""
+    if 'MI_ODE_DEFINE_DISCRETE_PLUGIN(' not in discrete_source:
+        raise ValueError('not a discrete plugin translation unit: the hypersolver gradient takes f with its generated vjp')
+    src = discrete_source.replace('#include "mi_ode_discrete_plugin.h"', '#include "mi_ode_hyper_grad_plugin.h"')
+    return src.replace('MI_ODE_DEFINE_DISCRETE_PLUGIN(', 'MI_ODE_DEFINE_HYPER_GRAD_PLUGIN(')
+
+
+_HYPER_GRAD_PLUGINS = {}
+
+
+def hyper_grad_plugin(source, dtype):
+    """(library, address of the mi_ode_hyper_grad_plugin table) of a hyper-grad translation unit (hyper_grad_source_of); compiled once,
+    cached by source and header hash."""
+    hit = _HYPER_GRAD_PLUGINS.get((source, dtype))
+    if hit is None:
+        from . import _plugin_build
+        lib = _plugin_build.build_and_load(source)
+        table = lib.mi_ode_hyper_grad_plugin_get(N.dtype_code(dtype))
+        if not table:
+            raise N.NativeError('hyper-grad plugin exports no table for %s' % dtype)
+        hit = (lib, int(table))
+        _HYPER_GRAD_PLUGINS[(source, dtype)] = hit
+    return hit
+
+
 def rows_source_of(rowlocal_source):
     """A row-local plugin translation unit (mi_ode_plugin.h) turned into the rows plugin of the same functor (per-trajectory step control)."""
     if 'MI_ODE_DEFINE_ROWLOCAL_PLUGIN(' not in rowlocal_source:
