@@ -38,10 +38,22 @@ __device__ __forceinline__ void quartic_fit(T y0, T y1, const T* k, T dt, const 
 }
 
 // interp._interp_evaluate (interp.py:39-67): x in the STATE dtype
+// In two halves, for callers that evaluate many elements at the same x (the linear tile pass forms the powers once per attempt):
+// p = {x, x^2, x^3, x^4}
+template <typename T>
+__device__ __forceinline__ void quartic_powers(T x, T* p) {
+  const T x2 = x * x, x3 = x2 * x, x4 = x3 * x;
+  p[0] = x; p[1] = x2; p[2] = x3; p[3] = x4;
+}
+template <typename T>
+__device__ __forceinline__ T quartic_eval_powers(const T* co, const T* p) {
+  return (((co[0] * p[3] + co[1] * p[2]) + co[2] * p[1]) + co[3] * p[0]) + co[4] * (T)1;
+}
 template <typename T>
 __device__ __forceinline__ T quartic_eval(const T* co, T x) {
-  const T x2 = x * x, x3 = x2 * x, x4 = x3 * x;
-  return (((co[0] * x4 + co[1] * x3) + co[2] * x2) + co[3] * x) + co[4] * (T)1;
+  T p[4];
+  quartic_powers<T>(x, p);
+  return quartic_eval_powers<T>(co, p);
 }
 
 template <typename T>

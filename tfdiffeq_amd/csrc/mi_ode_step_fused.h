@@ -633,6 +633,66 @@ __device__ __forceinline__ void lin_fill_coef(const StepArgs& A, T hs, T* coef) 
   }
 }
 
+// Dense output of the linear tile pass.  What step_emit needs per output j and does NOT depend on the element - t_out[j], and for the
+// quartic interpolants x_j = interp_x(t_start, t_new, t_out[j]) with its powers (a full division and three products) - is formed once
+// per pass into an LDS table next to `coef`, behind the same barrier.  step_emit inlined per element re-read t_out[j] through a generic
+// pointer (a flat load: it waits for vmcnt AND lgkmcnt, i.e. for the y1 / f1 stores issued just before it) and divided again, four times
+// per thread and tile.  Attempts with more than kLinEmitCap outputs form the abscissae in place as before.
+constexpr int kLinEmitCap = 16;
+template <typename T, bool TS>
+struct LinEmit {
+  using E = std::conditional_t<TS, double, T>;               // tsit5's weights are formed in float64 from t itself (tsit5_dense)
+  static constexpr int kPer = TS ? 1 : 4;                    // quartic: {x, x^2, x^3, x^4} (quartic_powers)
+  static constexpr int kSize = kLinEmitCap * kPer;
+};
+
+template <typename T, int S, bool TS>
+__device__ __forceinline__ void lin_fill_emit(const StepPlanes<T, S>& P, const double* t_out, typename LinEmit<T, TS>::E* tab) {
+  const int n = P.j_hi - P.j_lo;                             // (the caller checked n <= kLinEmitCap)
+  for (int q = threadIdx.x; q < n; q += blockDim.x) {
+    const double t = t_out[P.j_lo + q];
+    if constexpr (TS) tab[q] = t;
+    else quartic_powers<T>(interp_x<T>(P.t_start, P.t_new, t), tab + 4 * q);
+  }
+}
+
+// a table entry is the same for every lane, but an LDS read lands in vector registers: into scalar registers, the epilogue has none to spare
+__device__ __forceinline__ float lin_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ double lin_uniform(double v) {
+  const long long b = __double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// step_emit for the linear tile pass: the same operations per element and output, the same bits; the abscissa of an output comes from
+// the table (`use_tab`, wave-uniform) or is formed in place.  ONE loop for both sources: two loops cost the float64 kernel two more
+// spilled registers, this form eight fewer than step_emit alone.
+template <typename T, int S, bool TS>
+__device__ __forceinline__ void lin_emit(const StepArgs& A, const StepPlanes<T, S>& P, T y0, T y1, const T* k, T ymid, long long idx,
+                                         const double* t_out, const typename LinEmit<T, TS>::E* tab, bool use_tab) {
+  if (P.j_hi <= P.j_lo) return;
+  T* out = (T*)A.out;
+  if constexpr (TS) {
+    for (int j = P.j_lo; j < P.j_hi; ++j)
+      out[(long long)j * A.n_plane + idx] =
+          tsit5_dense<T, S + 1>(y0, k, P.t_start, P.t_new, use_tab ? lin_uniform(tab[j - P.j_lo]) : t_out[j], A.interp);
+  } else {
+    T co[5];
+    quartic_from_mid<T>(y0, y1, ymid, k[0], k[S], (T)P.dt64, co);
+    for (int j = P.j_lo; j < P.j_hi; ++j) {
+      T pw[4];
+      if (use_tab) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) pw[m] = lin_uniform(tab[4 * (j - P.j_lo) + m]);
+      } else {
+        quartic_powers<T>(interp_x<T>(P.t_start, P.t_new, t_out[j]), pw);
+      }
+      out[(long long)j * A.n_plane + idx] = quartic_eval_powers<T>(co, pw);
+    }
+  }
+}
+
 // SC0: read the streamed state with workgroup-scope (sc0, L1-bypassing) loads - needed when the kernel outlives an
 // attempt (whole-integration kernel: a plane is rewritten and re-read inside one launch)
 template <bool SC0, typename T>
@@ -654,6 +714,10 @@ __device__ __forceinline__ void lin_attempt_pass(const StepArgs& A, const StepPl
   using CF = LinCoef<S>;
   const long long ntiles = (A.batch + R_ - 1) / R_;
   lin_fill_coef<T, S>(A, P.hs, coef);
+  using EM = LinEmit<T, TS>;
+  __shared__ __attribute__((aligned(16))) typename EM::E s_emit[EM::kSize];
+  const bool emit_tab = P.j_hi - P.j_lo <= kLinEmitCap;      // (wave-uniform, like need_mid below)
+  if (emit_tab) lin_fill_emit<T, S, TS>(P, t_out, s_emit);
   lds_barrier();
   constexpr bool PF = LinCtx<T, D>::PF;                      // (streamed W: no registers for the prefetches - read at the point of use)
   T y0n[4], f0n[4];                                          // prefetched next tile (accumulator layout)
@@ -700,6 +764,14 @@ __device__ __forceinline__ void lin_attempt_pass(const StepArgs& A, const StepPl
       });
     };
     for_stages<1, S>(stage);
+    // The next tile's y0 / f0 were requested a whole tile ago and have landed.  "Using" them HERE, before the first store of this tile,
+    // puts the compiler's wait for them where only those loads and the previous tile's stores are outstanding.  Left to the loop
+    // latch - where the values are first read - it stands behind this tile's stores: one counter covers loads and stores, so the wait
+    // is for zero, i.e. for the acknowledgement of stores issued a moment before, with the matrix pipe idle.  (No instruction.)
+    if constexpr (PF) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(y0n[i]), "v"(f0n[i]) : "memory");
+    }
     const bool need_mid = !TS && P.j_hi > P.j_lo;            // (wave-uniform: an output time falls into this attempt)
     T err4[4], ym4[4];                                       // rk_common.py:60 / dopri5.py:42: step_finish's operations, one table
 #pragma unroll                                               // entry at a time (the coefficients are vector registers now)
@@ -732,7 +804,7 @@ __device__ __forceinline__ void lin_attempt_pass(const StepArgs& A, const StepPl
           ty1[cx.off_of(i)] = ys[i];
           tf1[cx.off_of(i)] = k[S][i];
         }
-        step_emit<T, S, TS>(A, P, y0e[i], ys[i], kk, ymid, idx, t_out);
+        lin_emit<T, S, TS>(A, P, y0e[i], ys[i], kk, ymid, idx, t_out, s_emit, emit_tab);
         acc.maxa = fmax(acc.maxa, (double)fabs(y0e[i]));
         acc.maxb = fmax(acc.maxb, (double)fabs(ys[i]));
         acc.suma += (double)err * (double)err;
@@ -771,6 +843,13 @@ __device__ __forceinline__ void lin_f0_pass(const StepArgs& A, const T* y0, T* f
     for (int i = 0; i < 4; ++i) { y0e[i] = y0n[i]; if constexpr (DOT) ge[i] = gn[i]; }
     if (PF && tile_i + nblk < ntiles) fetch(tile_i + nblk);
     cx.rhs_eval(y0e, kn);
+    if constexpr (PF) {                                      // the prefetch is "used" before this tile's stores (see lin_attempt_pass)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        asm volatile("" ::"v"(y0n[i]) : "memory");
+        if constexpr (DOT) asm volatile("" ::"v"(gn[i]) : "memory");
+      }
+    }
     const int nr = cx.rows_here(tile_i, A.batch);
     const long long tb = tile_i * R_ * cx.d;
 #pragma unroll
