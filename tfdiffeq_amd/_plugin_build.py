@@ -1,4 +1,5 @@
-"""Compile and load right-hand-side plugins (csrc/mi_ode_plugin.h): hipcc, gfx950, cached by source hash."""
+"""Compile and load right-hand-side plugins (csrc/mi_ode_plugin.h and the other kinds' headers: KINDS): hipcc, gfx950, cached by source hash."""
+import collections
 import ctypes as C
 import hashlib
 import os
@@ -11,6 +12,32 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-shared',
          '-I', N.CSRC, '-I', os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include')]
 _loaded = {}
+_tables = {}         # (kind, source, dtype) -> (library, table address): load()
+
+# The kinds of plugin: one row each.  `base` is the kind whose translation unit a derived kind is written from (derive() swaps the header
+# and the macro; None: the unit is generated as it is - rhs.CustomRowLocal / rhs.CustomCoop / lower), `not_base` the ValueError text when
+# derive() is handed something else (None: lenient - the text is returned with nothing replaced), `label` names the kind in load()'s error.
+Kind = collections.namedtuple('Kind', 'name header macro getter base not_base label')
+KINDS = {k.name: k for k in (
+    Kind('row-local', 'mi_ode_plugin.h', 'MI_ODE_DEFINE_ROWLOCAL_PLUGIN', 'mi_ode_plugin_get', None, None, 'plugin'),
+    Kind('coop', 'mi_ode_plugin.h', 'MI_ODE_DEFINE_COOP_PLUGIN', 'mi_ode_plugin_get', None, None, 'plugin'),
+    Kind('hyper', 'mi_ode_hyper_plugin.h', 'MI_ODE_DEFINE_HYPER_PLUGIN', 'mi_ode_hyper_plugin_get', 'row-local', None, 'hyper plugin'),
+    Kind('rows', 'mi_ode_rows_plugin.h', 'MI_ODE_DEFINE_ROWS_PLUGIN', 'mi_ode_rows_plugin_get', 'row-local',
+         'not a row-local plugin translation unit: the per-trajectory kernel takes one trajectory per thread', 'rows plugin'),
+    Kind('rows-t', 'mi_ode_rows_t_plugin.h', 'MI_ODE_DEFINE_ROWS_T_PLUGIN', 'mi_ode_rows_t_plugin_get', 'row-local',
+         'not a row-local plugin translation unit: the per-trajectory kernel takes one trajectory per thread', 'rows-t plugin'),
+    Kind('fixed-rows-t', 'mi_ode_fixed_rows_t_plugin.h', 'MI_ODE_DEFINE_FIXED_ROWS_T_PLUGIN', 'mi_ode_fixed_rows_t_plugin_get', 'row-local',
+         'not a row-local plugin translation unit: the fixed-grid kernel with per-row times takes one trajectory per thread', 'fixed-rows-t plugin'),
+    Kind('discrete', 'mi_ode_discrete_plugin.h', 'MI_ODE_DEFINE_DISCRETE_PLUGIN', 'mi_ode_discrete_plugin_get', None, None, 'discrete plugin'),
+    Kind('discrete-t', 'mi_ode_discrete_t_plugin.h', 'MI_ODE_DEFINE_DISCRETE_T_PLUGIN', 'mi_ode_discrete_t_plugin_get', 'discrete',
+         'not a discrete plugin translation unit: the reverse sweep takes f with its generated vjp', 'discrete-t plugin'),
+    Kind('hyper-grad', 'mi_ode_hyper_grad_plugin.h', 'MI_ODE_DEFINE_HYPER_GRAD_PLUGIN', 'mi_ode_hyper_grad_plugin_get', 'discrete',
+         'not a discrete plugin translation unit: the hypersolver gradient takes f with its generated vjp', 'hyper-grad plugin'),
+    Kind('rows-adjoint', 'mi_ode_rows_adjoint_plugin.h', 'MI_ODE_DEFINE_ROWS_ADJOINT_PLUGIN', 'mi_ode_rows_adjoint_plugin_get', None, None,
+         'rows-adjoint plugin'),
+    Kind('rows-adjoint-t', 'mi_ode_rows_adjoint_t_plugin.h', 'MI_ODE_DEFINE_ROWS_ADJOINT_T_PLUGIN', 'mi_ode_rows_adjoint_t_plugin_get', 'rows-adjoint',
+         'not a rows-adjoint plugin translation unit: the per-row adjoint kernel takes f with its generated vjp', 'rows-adjoint-t plugin'),
+)}
 
 
 def _owned_private(path):
@@ -116,11 +143,37 @@ def build_and_load(source):
     if lib is None:
         import torch  # noqa: F401  (same reason as _native.load: bind to torch's HIP runtime)
         lib = C.CDLL(path)
-        for name in ('mi_ode_plugin_get', 'mi_ode_hyper_plugin_get', 'mi_ode_discrete_plugin_get', 'mi_ode_rows_plugin_get',
-                     'mi_ode_rows_adjoint_plugin_get', 'mi_ode_rows_t_plugin_get', 'mi_ode_rows_adjoint_t_plugin_get',
-                     'mi_ode_fixed_rows_t_plugin_get', 'mi_ode_discrete_t_plugin_get', 'mi_ode_hyper_grad_plugin_get'):     # (one per kind of plugin)
+        for name in getter_names():
             if hasattr(lib, name):
                 getattr(lib, name).restype = C.c_void_p
                 getattr(lib, name).argtypes = [C.c_int]
         _loaded[path] = lib
     return lib
+
+
+def getter_names():
+    """The getter symbols build_and_load declares on a library: the registry's, each once."""
+    return tuple(dict.fromkeys(k.getter for k in KINDS.values()))
+
+
+def derive(kind, source):
+    """The translation unit of `kind` written from one of the kind it derives from: the same functor behind another header and macro."""
+    k = KINDS[kind]
+    base = KINDS[k.base]
+    if k.not_base is not None and base.macro + '(' not in source:
+        raise ValueError(k.not_base)
+    src = source.replace('#include "%s"' % base.header, '#include "%s"' % k.header)
+    return src.replace(base.macro + '(', k.macro + '(')
+
+
+def load(kind, source, dtype):
+    """(library, address of the table of `kind`) of a plugin translation unit; compiled once, cached by source and header hash."""
+    key = (kind, source, dtype)
+    hit = _tables.get(key)
+    if hit is None:
+        lib = build_and_load(source)
+        table = getattr(lib, KINDS[kind].getter)(N.dtype_code(dtype))
+        if not table:
+            raise N.NativeError('%s exports no table for %s' % (KINDS[kind].label, dtype))
+        hit = _tables[key] = (lib, int(table))
+    return hit

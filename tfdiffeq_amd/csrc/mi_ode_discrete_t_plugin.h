@@ -11,6 +11,7 @@
 // mi_ode_discrete_t_plugin_get(dtype) returns the table that goes into mi_ode_rhs.plugin of a mi_ode_discrete_row_sweep_t call.
 #pragma once
 #include "mi_ode_discrete_row_t.h"
+#include "mi_ode_plugin_getter.h"
 
 namespace mi {
 template <typename T, class RHS>
@@ -22,24 +23,4 @@ struct DiscreteTPlugin {
 };
 }  // namespace mi
 
-#if !defined(MI_ODE_PLUGIN_F32) && !defined(MI_ODE_PLUGIN_F64)
-#define MI_ODE_PLUGIN_F32 1
-#define MI_ODE_PLUGIN_F64 1
-#endif
-#ifdef MI_ODE_PLUGIN_F64
-#define MI_ODE_DISCRETE_T_CASE_F64(RHS) if (dtype == MI_ODE_F64) return mi::DiscreteTPlugin<double, RHS<double>>::table(MI_ODE_F64);
-#else
-#define MI_ODE_DISCRETE_T_CASE_F64(RHS)
-#endif
-#ifdef MI_ODE_PLUGIN_F32
-#define MI_ODE_DISCRETE_T_CASE_F32(RHS) if (dtype == MI_ODE_F32) return mi::DiscreteTPlugin<float, RHS<float>>::table(MI_ODE_F32);
-#else
-#define MI_ODE_DISCRETE_T_CASE_F32(RHS)
-#endif
-
-#define MI_ODE_DEFINE_DISCRETE_T_PLUGIN(RHS)                                                 \
-  extern "C" const mi_ode_discrete_row_t_plugin* mi_ode_discrete_t_plugin_get(int dtype) {   \
-    MI_ODE_DISCRETE_T_CASE_F64(RHS)                                                          \
-    MI_ODE_DISCRETE_T_CASE_F32(RHS)                                                          \
-    return nullptr;                                                                          \
-  }
+#define MI_ODE_DEFINE_DISCRETE_T_PLUGIN(RHS) MI_ODE_DEFINE_PLUGIN_GETTER(mi_ode_discrete_t_plugin_get, mi_ode_discrete_row_t_plugin, mi::DiscreteTPlugin, RHS)

@@ -10,6 +10,7 @@
 // includes mi_ode_hyper.h but no other plugin header: the caches of the forward's hyper plugins stay valid.
 #pragma once
 #include "mi_ode_hyper_grad.h"
+#include "mi_ode_plugin_getter.h"
 
 namespace mi {
 template <typename T, class RHS>
@@ -21,24 +22,4 @@ struct HyperGradPlugin {
 };
 }  // namespace mi
 
-#if !defined(MI_ODE_PLUGIN_F32) && !defined(MI_ODE_PLUGIN_F64)
-#define MI_ODE_PLUGIN_F32 1
-#define MI_ODE_PLUGIN_F64 1
-#endif
-#ifdef MI_ODE_PLUGIN_F64
-#define MI_ODE_HYPER_GRAD_CASE_F64(RHS) if (dtype == MI_ODE_F64) return mi::HyperGradPlugin<double, RHS<double>>::table(MI_ODE_F64);
-#else
-#define MI_ODE_HYPER_GRAD_CASE_F64(RHS)
-#endif
-#ifdef MI_ODE_PLUGIN_F32
-#define MI_ODE_HYPER_GRAD_CASE_F32(RHS) if (dtype == MI_ODE_F32) return mi::HyperGradPlugin<float, RHS<float>>::table(MI_ODE_F32);
-#else
-#define MI_ODE_HYPER_GRAD_CASE_F32(RHS)
-#endif
-
-#define MI_ODE_DEFINE_HYPER_GRAD_PLUGIN(RHS)                                                    \
-  extern "C" const mi_ode_hyper_grad_plugin* mi_ode_hyper_grad_plugin_get(int dtype) {          \
-    MI_ODE_HYPER_GRAD_CASE_F64(RHS)                                                             \
-    MI_ODE_HYPER_GRAD_CASE_F32(RHS)                                                             \
-    return nullptr;                                                                             \
-  }
+#define MI_ODE_DEFINE_HYPER_GRAD_PLUGIN(RHS) MI_ODE_DEFINE_PLUGIN_GETTER(mi_ode_hyper_grad_plugin_get, mi_ode_hyper_grad_plugin, mi::HyperGradPlugin, RHS)

@@ -24,6 +24,7 @@
 #include "mi_ode_persist.h"
 #include "mi_ode_adams.h"
 #include "mi_ode_adams_vc.h"
+#include "mi_ode_plugin_getter.h"
 
 #define MI_ODE_PLUGIN_ABI 3
 
@@ -124,42 +125,6 @@ struct CoopPlugin {
 
 }  // namespace mi
 
-// MI_ODE_PLUGIN_F32 / MI_ODE_PLUGIN_F64 select which state dtypes the plugin is built for (both by default)
-#if !defined(MI_ODE_PLUGIN_F32) && !defined(MI_ODE_PLUGIN_F64)
-#define MI_ODE_PLUGIN_F32 1
-#define MI_ODE_PLUGIN_F64 1
-#endif
-#ifdef MI_ODE_PLUGIN_F64
-#define MI_ODE_PLUGIN_CASE_F64(RHS) if (dtype == MI_ODE_F64) return mi::RowLocalPlugin<double, RHS<double>>::table(MI_ODE_F64);
-#else
-#define MI_ODE_PLUGIN_CASE_F64(RHS)
-#endif
-#ifdef MI_ODE_PLUGIN_F32
-#define MI_ODE_PLUGIN_CASE_F32(RHS) if (dtype == MI_ODE_F32) return mi::RowLocalPlugin<float, RHS<float>>::table(MI_ODE_F32);
-#else
-#define MI_ODE_PLUGIN_CASE_F32(RHS)
-#endif
-
-#define MI_ODE_DEFINE_ROWLOCAL_PLUGIN(RHS)                                               \
-  extern "C" const mi_ode_rowlocal_plugin* mi_ode_plugin_get(int dtype) {                \
-    MI_ODE_PLUGIN_CASE_F64(RHS)                                                          \
-    MI_ODE_PLUGIN_CASE_F32(RHS)                                                          \
-    return nullptr;                                                                      \
-  }
-
-#ifdef MI_ODE_PLUGIN_F64
-#define MI_ODE_COOP_CASE_F64(RHS) if (dtype == MI_ODE_F64) return mi::CoopPlugin<double, RHS<double>>::table(MI_ODE_F64);
-#else
-#define MI_ODE_COOP_CASE_F64(RHS)
-#endif
-#ifdef MI_ODE_PLUGIN_F32
-#define MI_ODE_COOP_CASE_F32(RHS) if (dtype == MI_ODE_F32) return mi::CoopPlugin<float, RHS<float>>::table(MI_ODE_F32);
-#else
-#define MI_ODE_COOP_CASE_F32(RHS)
-#endif
-#define MI_ODE_DEFINE_COOP_PLUGIN(RHS)                                                   \
-  extern "C" const mi_ode_rowlocal_plugin* mi_ode_plugin_get(int dtype) {                \
-    MI_ODE_COOP_CASE_F64(RHS)                                                            \
-    MI_ODE_COOP_CASE_F32(RHS)                                                            \
-    return nullptr;                                                                      \
-  }
+// (MI_ODE_PLUGIN_F32 / MI_ODE_PLUGIN_F64 select which state dtypes the plugin is built for: mi_ode_plugin_getter.h)
+#define MI_ODE_DEFINE_ROWLOCAL_PLUGIN(RHS) MI_ODE_DEFINE_PLUGIN_GETTER(mi_ode_plugin_get, mi_ode_rowlocal_plugin, mi::RowLocalPlugin, RHS)
+#define MI_ODE_DEFINE_COOP_PLUGIN(RHS) MI_ODE_DEFINE_PLUGIN_GETTER(mi_ode_plugin_get, mi_ode_rowlocal_plugin, mi::CoopPlugin, RHS)

@@ -16,6 +16,7 @@
 #pragma once
 #include "mi_ode_host.h"
 #include "mi_ode_rows_adjoint.h"
+#include "mi_ode_plugin_getter.h"
 
 namespace mi {
 template <typename T, class RHS>
@@ -27,24 +28,4 @@ struct RowsAdjPlugin {
 };
 }  // namespace mi
 
-#if !defined(MI_ODE_PLUGIN_F32) && !defined(MI_ODE_PLUGIN_F64)
-#define MI_ODE_PLUGIN_F32 1
-#define MI_ODE_PLUGIN_F64 1
-#endif
-#ifdef MI_ODE_PLUGIN_F64
-#define MI_ODE_ROWS_ADJOINT_CASE_F64(RHS) if (dtype == MI_ODE_F64) return mi::RowsAdjPlugin<double, RHS<double>>::table(MI_ODE_F64);
-#else
-#define MI_ODE_ROWS_ADJOINT_CASE_F64(RHS)
-#endif
-#ifdef MI_ODE_PLUGIN_F32
-#define MI_ODE_ROWS_ADJOINT_CASE_F32(RHS) if (dtype == MI_ODE_F32) return mi::RowsAdjPlugin<float, RHS<float>>::table(MI_ODE_F32);
-#else
-#define MI_ODE_ROWS_ADJOINT_CASE_F32(RHS)
-#endif
-
-#define MI_ODE_DEFINE_ROWS_ADJOINT_PLUGIN(RHS)                                                       \
-  extern "C" const mi_ode_rows_adjoint_plugin* mi_ode_rows_adjoint_plugin_get(int dtype) {           \
-    MI_ODE_ROWS_ADJOINT_CASE_F64(RHS)                                                                \
-    MI_ODE_ROWS_ADJOINT_CASE_F32(RHS)                                                                \
-    return nullptr;                                                                                  \
-  }
+#define MI_ODE_DEFINE_ROWS_ADJOINT_PLUGIN(RHS) MI_ODE_DEFINE_PLUGIN_GETTER(mi_ode_rows_adjoint_plugin_get, mi_ode_rows_adjoint_plugin, mi::RowsAdjPlugin, RHS)

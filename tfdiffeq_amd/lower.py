@@ -2106,7 +2106,7 @@ def classify(tr, generic=False, rows=1):
 # ---------------------------------------------------------------------------------------------
 # programs: the device side of a traced callable, cached by structure
 # ---------------------------------------------------------------------------------------------
-class _GeneratedRHS(R.DeviceRHS):
+class _GeneratedRHS(R._RowLocalKinds, R.DeviceRHS):
     """Generated device code behind the plugin ABI: `pool` carries the tensors (and the scalars beyond the eighth)."""
     kind = N.RHS_PLUGIN
     fixed_grid_fused = True
@@ -2119,6 +2119,7 @@ class _GeneratedRHS(R.DeviceRHS):
         self.coop = bool(coop)
         if coop:
             self.wide_tableaus = True
+            self.plugin_kind = 'coop'         # (the derived kinds are for row-local programs: the strict ones raise on this one's source)
         self.params = []
         self.pool = None
         self.torch_fn = None
@@ -2133,16 +2134,6 @@ class _GeneratedRHS(R.DeviceRHS):
 
     def source(self, dtype):
         return self._sources[dtype]
-
-    _plugin = R.CustomRowLocal._plugin
-    hyper_source = R.CustomRowLocal.hyper_source          # (row-local programs only: the hypersolver kernels take one trajectory per thread)
-    hyper_plugin = R.CustomRowLocal.hyper_plugin
-    rows_source = R.CustomRowLocal.rows_source            # (row-local programs only, likewise: the per-trajectory kernel)
-    rows_plugin = R.CustomRowLocal.rows_plugin
-    rows_t_source = R.CustomRowLocal.rows_t_source        # (... with per-row times, lengths and tolerances)
-    rows_t_plugin = R.CustomRowLocal.rows_t_plugin
-    fixed_rows_t_source = R.CustomRowLocal.fixed_rows_t_source        # (... and euler / rk4 with per-row times and lengths)
-    fixed_rows_t_plugin = R.CustomRowLocal.fixed_rows_t_plugin
 
     def fill(self, rhs, dtype, device):
         keep = super(_GeneratedRHS, self).fill(rhs, dtype, device)

@@ -16,6 +16,7 @@ import os
 import torch
 
 from . import _native as N
+from . import _plugin_build as PB
 
 
 class DeviceRHS(object):
@@ -396,7 +397,57 @@ MI_ODE_DEFINE_ROWLOCAL_PLUGIN(mi::RhsUser)
 """
 
 
-class CustomRowLocal(DeviceRHS):
+class _PluginKinds(object):
+    """What the plugin right-hand sides (CustomRowLocal, CustomCoop, lower._GeneratedRHS) share: `source(dtype)`, a translation unit of
+    `plugin_kind` (a row of _plugin_build.KINDS), compiled and loaded once per (kind, dtype) - `self._plugins`.  `cache_key()` asks for
+    `_plugin(dtype)` on every odeint call: a hit is one dictionary lookup, no source text is generated or hashed."""
+    plugin_kind = 'row-local'
+
+    def _plugin(self, dtype, kind=None):
+        """(library, address of the table) of this system's own plugin, or of the one of `kind` derived from it."""
+        key = (kind or self.plugin_kind, dtype)
+        hit = self._plugins.get(key)
+        if hit is None:
+            source = self.source(dtype)
+            hit = self._plugins[key] = PB.load(key[0], source if kind is None else PB.derive(kind, source), dtype)
+        return hit
+
+
+class _RowLocalKinds(_PluginKinds):
+    """... and the kinds derived from a row-local translation unit: the same functor behind the kernels of another header.  `<kind>_source`
+    is the text, `<kind>_plugin` the (library, address of the table) for `dtype`; compiled once, cached by source and header hash.  From a
+    cooperative unit (a lowered callable may be one) the strict kinds raise ValueError: their kernels take one trajectory per thread."""
+
+    def hyper_source(self, dtype):
+        """csrc/mi_ode_hyper_plugin.h: the hypersolver kernels."""
+        return PB.derive('hyper', self.source(dtype))
+
+    def hyper_plugin(self, dtype):
+        return self._plugin(dtype, 'hyper')
+
+    def rows_source(self, dtype):
+        """csrc/mi_ode_rows_plugin.h: the per-trajectory kernel."""
+        return PB.derive('rows', self.source(dtype))
+
+    def rows_plugin(self, dtype):
+        return self._plugin(dtype, 'rows')
+
+    def rows_t_source(self, dtype):
+        """csrc/mi_ode_rows_t_plugin.h: the per-trajectory kernel with per-row times, lengths and tolerances."""
+        return PB.derive('rows-t', self.source(dtype))
+
+    def rows_t_plugin(self, dtype):
+        return self._plugin(dtype, 'rows-t')
+
+    def fixed_rows_t_source(self, dtype):
+        """csrc/mi_ode_fixed_rows_t_plugin.h: the fixed-grid kernel (euler / rk4) with per-row times and lengths."""
+        return PB.derive('fixed-rows-t', self.source(dtype))
+
+    def fixed_rows_t_plugin(self, dtype):
+        return self._plugin(dtype, 'fixed-rows-t')
+
+
+class CustomRowLocal(_RowLocalKinds, DeviceRHS):
     """A trajectory-local system f(t, y) of small dimension written as device code.
 
     `body` is HIP C++ that fills `k[0..dim-1]` from `t`, `y[0..dim-1]` and the parameters `p[0..7]` (all of the state
@@ -438,18 +489,6 @@ class CustomRowLocal(DeviceRHS):
         return _PLUGIN_TEMPLATE.format(dtype_macro='MI_ODE_PLUGIN_F32' if dtype == torch.float32 else 'MI_ODE_PLUGIN_F64',
                                        dim=self.dim, body=body)
 
-    def _plugin(self, dtype):
-        hit = self._plugins.get(dtype)
-        if hit is None:
-            from . import _plugin_build
-            lib = _plugin_build.build_and_load(self.source(dtype))
-            table = lib.mi_ode_plugin_get(N.dtype_code(dtype))
-            if not table:
-                raise N.NativeError('plugin exports no table for %s' % dtype)
-            hit = (lib, int(table))
-            self._plugins[dtype] = hit
-        return hit
-
     def fill(self, rhs, dtype, device):
         keep = super(CustomRowLocal, self).fill(rhs, dtype, device)
         lib, table = self._plugin(dtype)
@@ -462,230 +501,55 @@ class CustomRowLocal(DeviceRHS):
     def cache_key(self, dtype, device):
         return super(CustomRowLocal, self).cache_key(dtype, device) + (self._plugin(dtype)[1],)
 
-    def hyper_source(self, dtype):
-        """The hyper plugin of this system (csrc/mi_ode_hyper_plugin.h): the same functor behind the hypersolver kernels."""
-        return hyper_source_of(self.source(dtype))
 
-    def hyper_plugin(self, dtype):
-        """(library, address of the mi_ode_hyper_plugin table) for `dtype`; compiled once, cached by source and header hash."""
-        plugins = self.__dict__.setdefault('_hyper_plugins', {})
-        hit = plugins.get(dtype)
-        if hit is None:
-            from . import _plugin_build
-            lib = _plugin_build.build_and_load(self.hyper_source(dtype))
-            table = lib.mi_ode_hyper_plugin_get(N.dtype_code(dtype))
-            if not table:
-                raise N.NativeError('hyper plugin exports no table for %s' % dtype)
-            hit = (lib, int(table))
-            plugins[dtype] = hit
-        return hit
-
-    def rows_source(self, dtype):
-        """The rows plugin of this system (csrc/mi_ode_rows_plugin.h): the same functor behind the per-trajectory kernel."""
-        return rows_source_of(self.source(dtype))
-
-    def rows_plugin(self, dtype):
-        """(library, address of the mi_ode_rows_plugin table) for `dtype`; compiled once, cached by source and header hash."""
-        plugins = self.__dict__.setdefault('_rows_plugins', {})
-        hit = plugins.get(dtype)
-        if hit is None:
-            from . import _plugin_build
-            lib = _plugin_build.build_and_load(self.rows_source(dtype))
-            table = lib.mi_ode_rows_plugin_get(N.dtype_code(dtype))
-            if not table:
-                raise N.NativeError('rows plugin exports no table for %s' % dtype)
-            hit = (lib, int(table))
-            plugins[dtype] = hit
-        return hit
-
-    def rows_t_source(self, dtype):
-        """The rows-t plugin of this system (csrc/mi_ode_rows_t_plugin.h): the same functor behind the per-trajectory kernel with per-row
-        times, lengths and tolerances."""
-        return rows_t_source_of(self.source(dtype))
-
-    def rows_t_plugin(self, dtype):
-        """(library, address of the mi_ode_rows_t_plugin table) for `dtype`; compiled once, cached by source and header hash."""
-        plugins = self.__dict__.setdefault('_rows_t_plugins', {})
-        hit = plugins.get(dtype)
-        if hit is None:
-            from . import _plugin_build
-            lib = _plugin_build.build_and_load(self.rows_t_source(dtype))
-            table = lib.mi_ode_rows_t_plugin_get(N.dtype_code(dtype))
-            if not table:
-                raise N.NativeError('rows-t plugin exports no table for %s' % dtype)
-            hit = (lib, int(table))
-            plugins[dtype] = hit
-        return hit
-
-    def fixed_rows_t_source(self, dtype):
-        """The fixed-rows-t plugin of this system (csrc/mi_ode_fixed_rows_t_plugin.h): the same functor behind the fixed-grid kernel with
-        per-row times and lengths."""
-        return fixed_rows_t_source_of(self.source(dtype))
-
-    def fixed_rows_t_plugin(self, dtype):
-        """(library, address of the mi_ode_fixed_rows_t_plugin table) for `dtype`; compiled once, cached by source and header hash."""
-        plugins = self.__dict__.setdefault('_fixed_rows_t_plugins', {})
-        hit = plugins.get(dtype)
-        if hit is None:
-            from . import _plugin_build
-            lib = _plugin_build.build_and_load(self.fixed_rows_t_source(dtype))
-            table = lib.mi_ode_fixed_rows_t_plugin_get(N.dtype_code(dtype))
-            if not table:
-                raise N.NativeError('fixed-rows-t plugin exports no table for %s' % dtype)
-            hit = (lib, int(table))
-            plugins[dtype] = hit
-        return hit
-
-
-_DISCRETE_PLUGINS = {}
-
-
-def discrete_plugin(source, dtype):
-    """(library, address of the mi_ode_discrete_row_plugin table) of a discrete plugin translation unit (lower.discrete_source:
-    csrc/mi_ode_discrete_plugin.h, f and its generated vjp behind the reverse-sweep kernel); compiled once, cached by source and header hash."""
-    hit = _DISCRETE_PLUGINS.get((source, dtype))
-    if hit is None:
-        from . import _plugin_build
-        lib = _plugin_build.build_and_load(source)
-        table = lib.mi_ode_discrete_plugin_get(N.dtype_code(dtype))
-        if not table:
-            raise N.NativeError('discrete plugin exports no table for %s' % dtype)
-        hit = (lib, table)
-        _DISCRETE_PLUGINS[(source, dtype)] = hit
-    return hit
-
-
-_ROWS_ADJOINT_PLUGINS = {}
-
-
-def rows_adjoint_plugin(source, dtype):
-    """(library, address of the mi_ode_rows_adjoint_plugin table) of a rows-adjoint plugin translation unit (lower.adjoint_source:
-    csrc/mi_ode_rows_adjoint_plugin.h, f and its generated vjp behind the per-trajectory adjoint kernel); compiled once, cached by source
-    and header hash."""
-    hit = _ROWS_ADJOINT_PLUGINS.get((source, dtype))
-    if hit is None:
-        from . import _plugin_build
-        lib = _plugin_build.build_and_load(source)
-        table = lib.mi_ode_rows_adjoint_plugin_get(N.dtype_code(dtype))
-        if not table:
-            raise N.NativeError('rows-adjoint plugin exports no table for %s' % dtype)
-        hit = (lib, table)
-        _ROWS_ADJOINT_PLUGINS[(source, dtype)] = hit
-    return hit
-
-
+# The derivers and loaders by name (solvers, discrete, rows_adjoint, hyper_solvers and the tests' source lists call these): a source of the
+# kind a plugin kind derives from (_plugin_build.KINDS) -> the derived text; (source, dtype) -> (library, address of the table).
 def hyper_source_of(rowlocal_source):
-    """A row-local plugin translation unit (mi_ode_plugin.h) turned into the hyper plugin of the same functor."""
-    src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_hyper_plugin.h"')
-    return src.replace('MI_ODE_DEFINE_ROWLOCAL_PLUGIN(', 'MI_ODE_DEFINE_HYPER_PLUGIN(')
-
-
-def hyper_grad_source_of(discrete_source):
-    """A discrete plugin translation unit (lower.discrete_source, mi_ode_discrete_plugin.h: f with its generated vjp) turned into the
-    hyper-grad plugin of the same functor (the one-launch gradient of a hypersolver call, csrc/mi_ode_hyper_grad_plugin.h)."""
-    if 'MI_ODE_DEFINE_DISCRETE_PLUGIN(' not in discrete_source:
-        raise ValueError('not a discrete plugin translation unit: the hypersolver gradient takes f with its generated vjp')
-    src = discrete_source.replace('#include "mi_ode_discrete_plugin.h"', '#include "mi_ode_hyper_grad_plugin.h"')
-    return src.replace('MI_ODE_DEFINE_DISCRETE_PLUGIN(', 'MI_ODE_DEFINE_HYPER_GRAD_PLUGIN(')
-
-
-_HYPER_GRAD_PLUGINS = {}
-
-
-def hyper_grad_plugin(source, dtype):
-    """(library, address of the mi_ode_hyper_grad_plugin table) of a hyper-grad translation unit (hyper_grad_source_of); compiled once,
-    cached by source and header hash."""
-    hit = _HYPER_GRAD_PLUGINS.get((source, dtype))
-    if hit is None:
-        from . import _plugin_build
-        lib = _plugin_build.build_and_load(source)
-        table = lib.mi_ode_hyper_grad_plugin_get(N.dtype_code(dtype))
-        if not table:
-            raise N.NativeError('hyper-grad plugin exports no table for %s' % dtype)
-        hit = (lib, int(table))
-        _HYPER_GRAD_PLUGINS[(source, dtype)] = hit
-    return hit
+    return PB.derive('hyper', rowlocal_source)
 
 
 def rows_source_of(rowlocal_source):
-    """A row-local plugin translation unit (mi_ode_plugin.h) turned into the rows plugin of the same functor (per-trajectory step control)."""
-    if 'MI_ODE_DEFINE_ROWLOCAL_PLUGIN(' not in rowlocal_source:
-        raise ValueError('not a row-local plugin translation unit: the per-trajectory kernel takes one trajectory per thread')
-    src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_rows_plugin.h"')
-    return src.replace('MI_ODE_DEFINE_ROWLOCAL_PLUGIN(', 'MI_ODE_DEFINE_ROWS_PLUGIN(')
+    return PB.derive('rows', rowlocal_source)
 
 
 def rows_t_source_of(rowlocal_source):
-    """A row-local plugin translation unit (mi_ode_plugin.h) turned into the rows-t plugin of the same functor (per-trajectory step control
-    with per-row times, lengths and tolerances)."""
-    if 'MI_ODE_DEFINE_ROWLOCAL_PLUGIN(' not in rowlocal_source:
-        raise ValueError('not a row-local plugin translation unit: the per-trajectory kernel takes one trajectory per thread')
-    src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_rows_t_plugin.h"')
-    return src.replace('MI_ODE_DEFINE_ROWLOCAL_PLUGIN(', 'MI_ODE_DEFINE_ROWS_T_PLUGIN(')
+    return PB.derive('rows-t', rowlocal_source)
 
 
 def fixed_rows_t_source_of(rowlocal_source):
-    """A row-local plugin translation unit (mi_ode_plugin.h) turned into the fixed-rows-t plugin of the same functor (euler / rk4 with
-    per-row times and lengths, csrc/mi_ode_fixed_rows_t_plugin.h)."""
-    if 'MI_ODE_DEFINE_ROWLOCAL_PLUGIN(' not in rowlocal_source:
-        raise ValueError('not a row-local plugin translation unit: the fixed-grid kernel with per-row times takes one trajectory per thread')
-    src = rowlocal_source.replace('#include "mi_ode_plugin.h"', '#include "mi_ode_fixed_rows_t_plugin.h"')
-    return src.replace('MI_ODE_DEFINE_ROWLOCAL_PLUGIN(', 'MI_ODE_DEFINE_FIXED_ROWS_T_PLUGIN(')
+    return PB.derive('fixed-rows-t', rowlocal_source)
+
+
+def hyper_grad_source_of(discrete_source):
+    return PB.derive('hyper-grad', discrete_source)
 
 
 def discrete_t_source_of(discrete_source):
-    """A discrete plugin translation unit (lower.discrete_source, mi_ode_discrete_plugin.h) turned into the discrete-t plugin of the same
-    functor (the reverse sweep over per-row times and lengths, csrc/mi_ode_discrete_t_plugin.h)."""
-    if 'MI_ODE_DEFINE_DISCRETE_PLUGIN(' not in discrete_source:
-        raise ValueError('not a discrete plugin translation unit: the reverse sweep takes f with its generated vjp')
-    src = discrete_source.replace('#include "mi_ode_discrete_plugin.h"', '#include "mi_ode_discrete_t_plugin.h"')
-    return src.replace('MI_ODE_DEFINE_DISCRETE_PLUGIN(', 'MI_ODE_DEFINE_DISCRETE_T_PLUGIN(')
-
-
-_DISCRETE_T_PLUGINS = {}
-
-
-def discrete_t_plugin(source, dtype):
-    """(library, address of the mi_ode_discrete_row_t_plugin table) of a discrete-t translation unit (discrete_t_source_of); compiled once,
-    cached by source and header hash."""
-    hit = _DISCRETE_T_PLUGINS.get((source, dtype))
-    if hit is None:
-        from . import _plugin_build
-        lib = _plugin_build.build_and_load(source)
-        table = lib.mi_ode_discrete_t_plugin_get(N.dtype_code(dtype))
-        if not table:
-            raise N.NativeError('discrete-t plugin exports no table for %s' % dtype)
-        hit = (lib, int(table))
-        _DISCRETE_T_PLUGINS[(source, dtype)] = hit
-    return hit
+    return PB.derive('discrete-t', discrete_source)
 
 
 def rows_adjoint_t_source_of(adjoint_source):
-    """A rows-adjoint plugin translation unit (lower.adjoint_source, mi_ode_rows_adjoint_plugin.h) turned into the rows-adjoint-t plugin of
-    the same functor (the per-trajectory adjoint with per-row times, lengths and tolerances)."""
-    if 'MI_ODE_DEFINE_ROWS_ADJOINT_PLUGIN(' not in adjoint_source:
-        raise ValueError('not a rows-adjoint plugin translation unit: the per-row adjoint kernel takes f with its generated vjp')
-    src = adjoint_source.replace('#include "mi_ode_rows_adjoint_plugin.h"', '#include "mi_ode_rows_adjoint_t_plugin.h"')
-    return src.replace('MI_ODE_DEFINE_ROWS_ADJOINT_PLUGIN(', 'MI_ODE_DEFINE_ROWS_ADJOINT_T_PLUGIN(')
+    return PB.derive('rows-adjoint-t', adjoint_source)
 
 
-_ROWS_ADJOINT_T_PLUGINS = {}
+def discrete_plugin(source, dtype):
+    return PB.load('discrete', source, dtype)
+
+
+def discrete_t_plugin(source, dtype):
+    return PB.load('discrete-t', source, dtype)
+
+
+def hyper_grad_plugin(source, dtype):
+    return PB.load('hyper-grad', source, dtype)
+
+
+def rows_adjoint_plugin(source, dtype):
+    return PB.load('rows-adjoint', source, dtype)
 
 
 def rows_adjoint_t_plugin(source, dtype):
-    """(library, address of the mi_ode_rows_adjoint_t_plugin table) of a rows-adjoint-t translation unit (rows_adjoint_t_source_of);
-    compiled once, cached by source and header hash."""
-    hit = _ROWS_ADJOINT_T_PLUGINS.get((source, dtype))
-    if hit is None:
-        from . import _plugin_build
-        lib = _plugin_build.build_and_load(source)
-        table = lib.mi_ode_rows_adjoint_t_plugin_get(N.dtype_code(dtype))
-        if not table:
-            raise N.NativeError('rows-adjoint-t plugin exports no table for %s' % dtype)
-        hit = (lib, int(table))
-        _ROWS_ADJOINT_T_PLUGINS[(source, dtype)] = hit
-    return hit
-
+    return PB.load('rows-adjoint-t', source, dtype)
 
 _COOP_TEMPLATE = """// generated by tfdiffeq_amd.rhs.CustomCoop - do not edit
 #define {dtype_macro} 1
@@ -724,7 +588,7 @@ MI_ODE_DEFINE_COOP_PLUGIN(mi::RhsUserCoop)
 """
 
 
-class CustomCoop(DeviceRHS):
+class CustomCoop(_PluginKinds, DeviceRHS):
     """A system f(t, y) of dimension up to 256 written as device code for ONE state element (round 5; round-4 review, item 5: user code
     beyond what a thread can keep - coupled oscillator chains, stencils, a dense layer with the user's own pointwise function).
 
@@ -742,6 +606,7 @@ class CustomCoop(DeviceRHS):
     kind = N.RHS_PLUGIN
     MAX_DIM = 256
     row_local = False
+    plugin_kind = 'coop'
     fixed_grid_fused = True       # euler / rk4 (3/8 rule) in one launch, any batch size (trajectories never interact on a fixed grid)
     multistep_fused = True
     wide_tableaus = True          # (solvers._make_engine: dopri8 / adaptive_heun exist for this family - the same whole-call kernel)
@@ -769,8 +634,6 @@ class CustomCoop(DeviceRHS):
     def source(self, dtype):
         body = '\n'.join('      ' + ln for ln in self.body.strip().splitlines())
         return _COOP_TEMPLATE.format(dtype_macro='MI_ODE_PLUGIN_F32' if dtype == torch.float32 else 'MI_ODE_PLUGIN_F64', dim=self.dim, body=body)
-
-    _plugin = CustomRowLocal._plugin
 
     def fill(self, rhs, dtype, device):
         keep = super(CustomCoop, self).fill(rhs, dtype, device)
