@@ -276,6 +276,25 @@ int mi_ode_integrate_rows(mi_ode_handle h, const void* rows_plugin, const void* 
 int mi_ode_integrate_rows_t(mi_ode_handle h, const void* rows_t_plugin, const void* y0_dev, const double* t_dev, int32_t T,
                             const int32_t* len_dev, const double* rtol_dev, const double* atol_dev, void* out_dev,
                             int64_t* row_stats_dev, mi_ode_stats* stats, void* stream);
+/* Per-trajectory step control for the ODEFunc network on the matrix cores (csrc/mi_ode_rows_mlp.h): the same call for a handle of the
+ * fp32 MLP tile family.  A 32-row tile runs through the whole call with the weights resident; the control flow is workgroup-uniform and
+ * every row of the tile has its own initial step, error ratio over its dim elements, accept / reject sequence, output cursor and dense
+ * output, max_num_steps and dt-underflow checks.  A row's numbers do not depend on the rows it shares a tile with: out_dev[:, i] is what
+ * the call computes for y0[i] alone, bit for bit, however the batch is sliced or ordered.  One launch for any batch size, no
+ * co-residency requirement.
+ *   h             an adaptive float32 handle created for an MI_ODE_RHS_MLP right-hand side inside the tile kernels' box (dim <= 64,
+ *                 hidden <= 128; relu, softplus or tanh; with or without the time input), the FSAL shaped 6-row (dopri5, tsit5) or 3-row
+ *                 (bosh3) tableau, one state tensor, one rank - anything else: MI_ODE_E_INVALID
+ *   desc          launch options (below); sizeof(mi_ode_rows_mlp_desc) = mi_ode_rows_mlp_sizeof()
+ *   row_stats_dev, stats, the return value: as for mi_ode_integrate_rows */
+typedef struct mi_ode_rows_mlp_desc {
+  int32_t grid;               /* 0: the library chooses (a workgroup per 32-row tile, capped); > 0: at most this many workgroups - they
+                                 loop over the tiles (results do not depend on it) */
+  int32_t reserved;           /* 0 */
+} mi_ode_rows_mlp_desc;
+int mi_ode_integrate_rows_mlp(mi_ode_handle h, const mi_ode_rows_mlp_desc* desc, const void* y0_dev, const double* t_host, int32_t T,
+                              void* out_dev, int64_t* row_stats_dev, mi_ode_stats* stats, void* stream);
+int64_t mi_ode_rows_mlp_sizeof(void);                     /* sizeof(mi_ode_rows_mlp_desc), for a binding's layout check */
 /* A fixed-grid solve (euler / rk4 on the default grid) with output times and a length of every row's own (csrc/mi_ode_fixed_rows_t.h).
  * Row i of out_dev is what mi_ode_fixed_grid_integrate returns for y0[i] alone with the times t_dev[i][0 .. len_i - 1], bit for bit;
  * out_dev[k][i] for k >= len_i is exactly 0 and t_dev[i][len_i ..] is never read.

@@ -126,6 +126,11 @@ class AdjointRowsDesc(C.Structure):
 ROWS_ADJOINT_MAX_AUG, ROWS_ADJOINT_THREADS = 32, 256
 
 
+class RowsMlpDesc(C.Structure):
+    """mi_ode_rows_mlp_desc: launch options of per-trajectory step control on the MLP tile kernel (grid 0: the library chooses)."""
+    _fields_ = [('grid', C.c_int32), ('reserved', C.c_int32)]
+
+
 class AdjointRowsTDesc(C.Structure):
     """mi_ode_adjoint_rows_t_desc: the same with every row's own output times, length and tolerances."""
     _fields_ = [('dtype', C.c_int32), ('n_times', C.c_int32), ('batch', C.c_int64), ('dim', C.c_int32), ('n_params', C.c_int32),
@@ -235,6 +240,9 @@ _PROTOS = {
                                         C.POINTER(Stats), C.c_void_p]),
     'mi_ode_integrate_rows_t': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_integrate_rows_mlp': (C.c_int, [C.c_void_p, C.POINTER(RowsMlpDesc), C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.POINTER(Stats), C.c_void_p]),
+    'mi_ode_rows_mlp_sizeof': (C.c_int64, []),
     'mi_ode_integrate_fixed_rows_t': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                 C.POINTER(Stats), C.c_void_p]),
     'mi_ode_fixed_grid_integrate': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p,
@@ -401,6 +409,8 @@ def load():
         raise NativeError('struct layout mismatch for AdjointRowsDesc: C %d vs ctypes %d' % (lib.mi_ode_adjoint_rows_sizeof(), C.sizeof(AdjointRowsDesc)))
     if lib.mi_ode_adjoint_rows_t_sizeof() != C.sizeof(AdjointRowsTDesc):
         raise NativeError('struct layout mismatch for AdjointRowsTDesc: C %d vs ctypes %d' % (lib.mi_ode_adjoint_rows_t_sizeof(), C.sizeof(AdjointRowsTDesc)))
+    if lib.mi_ode_rows_mlp_sizeof() != C.sizeof(RowsMlpDesc):
+        raise NativeError('struct layout mismatch for RowsMlpDesc: C %d vs ctypes %d' % (lib.mi_ode_rows_mlp_sizeof(), C.sizeof(RowsMlpDesc)))
     if lib.mi_ode_discrete_row_t_sizeof() != C.sizeof(DiscreteRowTDesc):
         raise NativeError('struct layout mismatch for DiscreteRowTDesc: C %d vs ctypes %d' % (lib.mi_ode_discrete_row_t_sizeof(), C.sizeof(DiscreteRowTDesc)))
     if lib.mi_ode_hyper_grad_sizeof() != C.sizeof(HyperGradDesc):

@@ -138,3 +138,8 @@ struct RowsKernels {
 // the catalogue families' kernels, one translation unit per state dtype (mi_ode_rows.hip, mi_ode_rows_f32.hip)
 const void* mi_rows_fn_f64(int family, int S, int ts_dense, int fsal);
 const void* mi_rows_fn_f32(int family, int S, int ts_dense, int fsal);
+// host helpers the per-trajectory entry points share (mi_ode_rows.hip): the handle's staging arrays for n output times, and its tableau,
+// right-hand side and controller parameters as the kernels get them
+struct mi_ode_solver;
+int mi_rows_ensure_t_out(mi_ode_solver* h, int n);
+void mi_rows_step_args(mi_ode_solver* h, mi::StepArgs& A);

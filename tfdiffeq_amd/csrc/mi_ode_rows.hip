@@ -17,10 +17,8 @@ const void* mi_rows_fn_f64(int family, int S, int ts_dense, int fsal) {
   }
 }
 
-namespace {
-
 // the output times beyond those that travel as kernel arguments: the handle's device / pinned staging arrays, grown on demand
-int rows_ensure_t_out(mi_ode_solver* h, int n) {
+int mi_rows_ensure_t_out(mi_ode_solver* h, int n) {
   if (n > h->t_out_cap) {
     if (h->t_out_dev) (void)hipFree(h->t_out_dev);
     h->t_out_dev = nullptr; h->t_out_cap = 0;
@@ -39,7 +37,7 @@ int rows_ensure_t_out(mi_ode_solver* h, int n) {
 }
 
 // tableau, right-hand side and controller parameters of the handle, as the shared kernels get them
-void rows_step_args(mi_ode_solver* h, StepArgs& A) {
+void mi_rows_step_args(mi_ode_solver* h, StepArgs& A) {
   memset(&A, 0, sizeof(A));
   A.ctl = h->ctl; A.planes = h->planes; A.stride = h->stride; A.batch = h->d.batch; A.dim = (int)h->d.dim;
   A.interp = h->d.interp; A.out = h->cur_out; A.t_out = h->t_out_dev; A.n_plane = h->n;
@@ -48,6 +46,8 @@ void rows_step_args(mi_ode_solver* h, StepArgs& A) {
   A.ticket = nullptr;
   A.cp = h->cp;
 }
+
+namespace {
 
 bool rows_family(const mi_ode_solver* h) {
   return h->family == FAM_CUBIC2 || h->family == FAM_LINEAR2 || h->family == FAM_LV || h->family == FAM_LORENZ || h->family == FAM_PLUGIN;
@@ -92,7 +92,7 @@ extern "C" int mi_ode_integrate_rows(mi_ode_handle h, const void* rows_plugin, c
   const int n_out = T - 1;
   if (n_out > kPersistTSmall) {
     MI_HIP(hipStreamSynchronize(st));          // the pinned staging buffer may still be in flight from a previous call
-    const int rc = rows_ensure_t_out(h, n_out);
+    const int rc = mi_rows_ensure_t_out(h, n_out);
     if (rc != 0) return rc;
     memcpy(h->t_out_host, t_host + 1, (size_t)n_out * sizeof(double));
     MI_HIP(hipMemcpyAsync(h->t_out_dev, h->t_out_host, (size_t)n_out * sizeof(double), hipMemcpyHostToDevice, st));
@@ -103,7 +103,7 @@ extern "C" int mi_ode_integrate_rows(mi_ode_handle h, const void* rows_plugin, c
   RowsArgs R;
   memset(&R, 0, sizeof(R));
   PersistArgs& A = R.p;
-  rows_step_args(h, A.s);
+  mi_rows_step_args(h, A.s);
   A.y0 = y0_dev; A.out0 = out_dev; A.n_out = n_out;
   A.t0 = t_host[0];
   A.first_dt = h->cp.auto_first_step ? 0.0 : h->d.first_step;

@@ -18,6 +18,7 @@ AUTO, STAGE, STEP, WHOLE = (FUSION[k] for k in ('auto', 'stage', 'step', 'whole'
 #        fused_tuple      rhs.PerComponent over one segmented (adaptive) or concatenated (fixed grid) buffer
 #        fused_multistep  the one-launch fixed-order / variable-order Adams kernels
 #        fused_rows       options['per_trajectory']: every row an integration of its own on k_rows_rowlocal (no fallback: refused or run)
+#        fused_rows_mlp   options['per_trajectory'] for the float32 ODEFunc network: a 32-row tile per workgroup on k_rows_mlp, every row its own control
 #        callable         graph_step.DeviceControlledRK: f as a callable, the controller on the device
 #        planes           the host loop over plane kernels
 # rhs: the DeviceRHS a fused engine is built from.  why: the predicate that decided.  told: a descriptor whose family has no kernel for
@@ -107,14 +108,41 @@ def rows_method_refusal(solver_cls):
             'control only - per-trajectory step control exists for %s' % (getattr(solver_cls, '__name__', solver_cls), ROWS_TABLEAUS))
 
 
-def rows_family_why(name, dim):
+ROWS_MLP_WHY = 'per-trajectory step control on the MLP tile kernel: a 32-row tile per workgroup, every row its own control, one launch'
+ROWS_MLP_TABLEAUS = 'dopri5, tsit5 and bosh3'
+ROWS_MLP_BOX = ('the float32 ODEFunc network (rhs.MLP, rhs.from_sequential, models.ODEFunc, a lowered Linear / activation / Linear / activation / '
+                'Linear) with dim <= %d and hidden <= %d on %s' % (R.MLP.MAX_DIM, R.MLP.MAX_HIDDEN, ROWS_MLP_TABLEAUS))
+ROWS_MLP_T_REFUSAL = ('per-row times, lengths or tolerances (a 2-D `t`, options[\'t_lengths\'], `rtol` / `atol` tensors) with the ODEFunc network: '
+                      'k_rows_mlp reads one `t` and one tolerance pair for all rows - pass a 1-D `t` and scalar tolerances')
+
+
+def rows_family_why(name, dim, also=''):
+    """also: what the caller's route takes beyond the trajectory-per-thread right-hand sides (the adaptive route: ROWS_MLP_BOX)."""
     return ('a right-hand side on the matrix-core or cooperative kernels (%s, dim %s): f is evaluated by the threads of a workgroup '
             'together there, and a barrier under per-lane control flow cannot be - per-trajectory control takes rhs.Lorenz, '
-            'rhs.LotkaVolterra, 2 x 2 rhs.Linear / rhs.CubicLinear, rhs.CustomRowLocal and lowered callables of at most 32 elements' % (name, dim))
+            'rhs.LotkaVolterra, 2 x 2 rhs.Linear / rhs.CubicLinear, rhs.CustomRowLocal and lowered callables of at most 32 elements%s'
+            % (name, dim, (', and ' + also) if also else ''))
+
+
+def rows_mlp_refusal(dev, y, rows, fsal, quartic=True):
+    """'' when k_rows_mlp (csrc/mi_ode_rows_mlp.h) takes an options['per_trajectory'] call of the rhs.MLP `dev`, else the reason.  Pure."""
+    name = type(dev).__name__
+    if not (isinstance(y, torch.Tensor) and y.dim() >= 1 and y.numel() > 0 and y.shape[-1] == dev.dim):
+        return rows_family_why(name, dev.dim, ROWS_MLP_BOX) + ': the state must be a non-empty [batch, %d] tensor' % dev.dim
+    if y.dtype != torch.float32:
+        return rows_family_why(name, dev.dim, ROWS_MLP_BOX) + (': this state is %s (the float64 tile kernel has no registers left for a '
+                                                               'row\'s own step, time and record)' % str(y.dtype).replace('torch.', ''))
+    if dev.dim > R.MLP.MAX_DIM or dev.hidden > R.MLP.MAX_HIDDEN:
+        return rows_family_why(name, dev.dim, ROWS_MLP_BOX) + ': this network is %d -> %d (outside the tile kernels\' box)' % (dev.dim, dev.hidden)
+    if not ((fsal and rows == 3 and quartic) or (fsal and rows == 6)):
+        named = {13: 'dopri8', 1: 'adaptive_heun'}.get(rows, 'this method')
+        return ('a %d-row tableau (%s) the per-trajectory MLP tile kernel is not instantiated for: it is for %s (a tile keeps k_1 .. k_S of '
+                'its rows in registers next to the resident weights)' % (rows, named, ROWS_MLP_TABLEAUS))
+    return ''
 
 
 def rows_refusal(func, y0, rows, fsal, *, quartic=True, force_planes=False, group=False):
-    """'' when k_rows_rowlocal (csrc/mi_ode_rows.h) takes this call, else the reason options['per_trajectory'] is refused with.  Pure: reads
+    """'' when k_rows_rowlocal (csrc/mi_ode_rows.h) - for an rhs.MLP: k_rows_mlp - takes this call, else the reason options['per_trajectory'] is refused with.  Pure: reads
     the descriptor behind `func`, shapes and dtypes - never the device."""
     dev = getattr(func, 'device_rhs', None)
     if getattr(func, 'per_component', False) or len(y0) != 1:
@@ -128,8 +156,10 @@ def rows_refusal(func, y0, rows, fsal, *, quartic=True, force_planes=False, grou
         return ('a Python callable that was not lowered: only a right-hand side that runs on the trajectory-per-thread kernels can have '
                 'per-trajectory control')
     y = y0[0]
+    if isinstance(dev, R.MLP):
+        return rows_mlp_refusal(dev, y, rows, fsal, quartic)
     if not getattr(dev, 'row_local', False) or not (isinstance(y, torch.Tensor) and y.dim() >= 1 and y.numel() > 0 and dev.supports(y)):
-        return rows_family_why(type(dev).__name__, getattr(dev, 'dim', None))
+        return rows_family_why(type(dev).__name__, getattr(dev, 'dim', None), ROWS_MLP_BOX)
     one_row = rows == 1 and not fsal
     if not ((fsal and rows in (3, 13) and quartic) or (fsal and rows == 6) or (one_row and quartic)):
         return 'a %d-row tableau the per-trajectory kernel is not instantiated for (it is for %s)' % (rows, ROWS_TABLEAUS)
@@ -251,11 +281,13 @@ def rows_adjoint_refusal(dim, n_params, adjoint_method, adjoint_rtol, adjoint_at
 
 def adaptive_rk(func, y0, rows, fsal, *, quartic=True, force_planes=False, group=False, fusion=AUTO, graph='auto', per_trajectory=False):
     """The adaptive Runge-Kutta solvers.  rows, fsal: the tableau's shape; quartic: the dense output is the quartic through the midpoint.
-    per_trajectory: every row of the batch is an integration of its own (k_rows_rowlocal) - or a ValueError: never shared control."""
+    per_trajectory: every row of the batch is an integration of its own (k_rows_rowlocal, k_rows_mlp) - or a ValueError: never shared control."""
     if per_trajectory:
         why = rows_refusal(func, y0, rows, fsal, quartic=quartic, force_planes=force_planes, group=group)
         if why:
             raise ValueError("options['per_trajectory'] refused: " + why)
+        if isinstance(func.device_rhs, R.MLP):
+            return Route('fused_rows_mlp', func.device_rhs, ROWS_MLP_WHY)
         return Route('fused_rows', func.device_rhs, ROWS_WHY)
 
     def host(why, told=None):

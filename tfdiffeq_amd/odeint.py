@@ -226,7 +226,12 @@ def _per_trajectory_target(func, y0, method, options, _adjoint=False):
     opts = dict(options, per_trajectory=True)
     if getattr(func, 'stage_rhs', None) is not None:
         refuse(D.rows_family_why(type(func).__name__, getattr(func, 'dim', None)))
+    from . import rhs as _rhs
+    mlp_grad = ('gradients of a per-trajectory solve of the ODEFunc network: its forward route (k_rows_mlp: plain odeint with the option, no '
+                'gradients) has no backward kernel - call odeint_adjoint without the option (shared control, the fused adjoint kernel)')
     if _descriptor(func):
+        if _adjoint and isinstance(func, _rhs.MLP):
+            refuse(mlp_grad)
         opts.pop('lower', None)
         return None, opts
     if not callable(func):
@@ -246,8 +251,12 @@ def _per_trajectory_target(func, y0, method, options, _adjoint=False):
         refuse('tracing this callable failed (%s: %s), and a Python callable has shared control only' % (type(e).__name__, e))
     if not _adjoint and torch.is_grad_enabled() and any(isinstance(e['t'], torch.Tensor) and e['t'].requires_grad for e in low.trace.tensors):
         refuse(grad)
+    if low.kind == 'mlp' and isinstance(low.rhs, _rhs.MLP):
+        if _adjoint:
+            refuse(mlp_grad)
+        return low, opts                                  # (k_rows_mlp or its own refusal: the solver's route decides, dispatch.rows_mlp_refusal)
     if not getattr(low.rhs, 'row_local', False):
-        refuse(D.rows_family_why("a lowered '%s' program" % low.kind, low.dim))
+        refuse(D.rows_family_why("a lowered '%s' program" % low.kind, low.dim, D.ROWS_MLP_BOX))
     return low, opts
 
 
@@ -273,6 +282,10 @@ def _odeint_per_trajectory(func, y0, t, rtol, atol, method, options):
             opts['t_lengths'] = options['t_lengths']
         return _run_lowered(low, func, y0, t, rtol, atol, method, opts)     # (t, rtol, atol and the lengths travel as they are: the rows of the
     if wanted:                                                              #  state keep their order under its reshape)
+        from . import dispatch as D
+        from . import rhs as _rhs
+        if isinstance(func, _rhs.MLP):                                      # (k_rows_mlp has one `t` and one tolerance pair: said before anything is moved)
+            raise ValueError("options['per_trajectory'] refused: " + D.ROWS_MLP_T_REFUSAL)
         rt, _ = rows_times.prepare(y0, t, rtol, atol, options)
         # misc._check_inputs on a stand-in for the direction the rows share: the sign goes to the right-hand side as for a 1-D t
         tensor_input, f, state, _ = _check_inputs(func, y0, [0., -1.] if rt.decreasing else [0., 1.])

@@ -131,6 +131,16 @@ def plan_rows(func, y0, rtol, atol, method, opts, t=None):
         return {'engine': 'refused', 'kernel': None, 'launches': None, 'per_trajectory': True, 'why': str(e), 'lower': None}
     y, rhs, S = ys[0], route.rhs, len(solver.tableau.alpha)
     fam = D.family(rhs)
+    lower = None if low is None else {'lowered': True, 'kind': low.kind, 'dim': low.dim, 'batch_axes': low.trace.nb}
+    if route.kind == 'fused_rows_mlp':
+        if per_row_t:
+            return {'engine': 'refused', 'kernel': None, 'launches': None, 'per_trajectory': True,
+                    'why': "options['per_trajectory'] refused: " + D.ROWS_MLP_T_REFUSAL, 'lower': None}
+        dp, hp = (16 if rhs.dim <= 16 else 64), (16 if rhs.hidden <= 16 else 128)
+        return {'engine': 'fused', 'kernel': 'k_rows_mlp<%d, %d, %s, %d, ..> (a 32-row tile per workgroup with the weights resident, every row its own '
+                                             'control, a loop over tiles: any batch size, no grid hand-off)' % (dp, hp, rhs.activation, S),
+                'launches': 'one per call', 'why': D.ROWS_MLP_WHY, 'per_trajectory': True, 'family': FAMILY.get(fam, fam),
+                'state': '%d x %d %s' % (y.numel() // max(int(rhs.dim or 1), 1), rhs.dim, str(y.dtype).replace('torch.', '')), 'lower': lower}
     kernel, why = ('k_rows_rowlocal_t<%s, %d, ..> (a trajectory per thread with its own times, length and tolerances, any batch size, no grid hand-off)',
                    D.ROWS_T_WHY) if per_row_t else ('k_rows_rowlocal<%s, %d, ..> (a trajectory per thread, any batch size, no grid hand-off)', D.ROWS_WHY)
     return {'engine': 'fused', 'kernel': kernel % (TNAME[y.dtype], S),

@@ -348,6 +348,21 @@ class _FusedEngine(object):
                                                         self._stream()), 'mi_ode_integrate_rows')
         return out, rows, rc
 
+    def integrate_rows_mlp(self, t, y0=None, grid=0):
+        """Per-trajectory step control for the float32 ODEFunc network (mi_ode_integrate_rows_mlp): as integrate_rows.  grid: 0 - the
+        library chooses; > 0 - at most that many workgroups loop over the 32-row tiles (the results do not depend on it)."""
+        y0 = self._check_y0(y0)
+        arr, p = self._times(t)
+        T = arr.shape[0]
+        out = torch.empty((T,) + self.shape, dtype=self.dtype, device=self.device)
+        rows = torch.empty((self.batch, 4), dtype=torch.int64, device=self.device)
+        desc = N.RowsMlpDesc(grid=int(grid), reserved=0)
+        with torch.cuda.device(self.device):
+            rc = N.check(self.lib.mi_ode_integrate_rows_mlp(self.h, C.byref(desc), C.c_void_p(y0.data_ptr()), p, T, C.c_void_p(out.data_ptr()),
+                                                            C.c_void_p(rows.data_ptr()), C.byref(self.stats), self._stream()),
+                         'mi_ode_integrate_rows_mlp')
+        return out, rows, rc
+
     def integrate_rows_t(self, rt, y0=None, rows_t_plugin=None):
         """Per-trajectory step control with per-row times, lengths and tolerances (mi_ode_integrate_rows_t): as integrate_rows.  rt: a
         rows_times.RowsTimes whose tensors are on this engine's device; rows_t_plugin: (library, table) of a plugin's rows-t plugin."""
@@ -811,6 +826,11 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
         # sequence, output cursor and assertions - what one call per row y0[i:i+1] computes, in one launch.  False: the reference's
         # semantics (one norm over the batch)
         self._per_trajectory = D.per_trajectory_option({'per_trajectory': unused_kwargs.pop('per_trajectory', False)})[1]
+        # per_trajectory on the MLP tile kernel (csrc/mi_ode_rows_mlp.h): 0 - a workgroup per 32-row tile (capped); > 0 - at most that many
+        # workgroups, which loop over the tiles (a tuning and test knob: the results do not depend on it)
+        self._rows_grid = int(unused_kwargs.pop('rows_grid', 0))
+        if self._rows_grid < 0:
+            raise ValueError("options['rows_grid'] must be >= 0")
         _handle_unused_kwargs(self, unused_kwargs)
         self.func = func
         self.y0 = y0
@@ -897,7 +917,8 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
 
     def integrate_rows_t(self, rt):
         """integrate() for per-row times, lengths and tolerances (rows_times.RowsTimes, checked there): k_rows_rowlocal_t."""
-        self.route()                                             # (a refusal is a ValueError of the call, whatever device y0 is on)
+        if self.route().kind == 'fused_rows_mlp':                # (a refusal is a ValueError of the call, whatever device y0 is on)
+            raise ValueError("options['per_trajectory'] refused: " + D.ROWS_MLP_T_REFUSAL)
         for y_ in self.y0:
             N.require_gpu_tensor(y_, 'y0')
         route = self.route()
@@ -910,7 +931,11 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
         times, lengths and tolerances in place of t (k_rows_rowlocal_t, likewise)."""
         rhs, y = route.rhs, self.y0[0]
         eng = self._make_engine(route)
-        if rt is None:
+        if route.kind == 'fused_rows_mlp':
+            times = t.to(torch.float64).numpy()
+            out, rows, bits = eng.integrate_rows_mlp(times, y, self._rows_grid)
+            engine = 'k_rows_mlp: ' + D.ROWS_MLP_WHY
+        elif rt is None:
             plugin = rhs.rows_plugin(y.dtype) if rhs.kind == N.RHS_PLUGIN else None
             times = t.to(torch.float64).numpy()
             out, rows, bits = eng.integrate_rows(times, y, plugin)
@@ -921,7 +946,7 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
             plugin = rhs.rows_t_plugin(y.dtype) if rhs.kind == N.RHS_PLUGIN else None
             out, rows, bits = eng.integrate_rows_t(rt, y, plugin)
             engine = 'k_rows_rowlocal_t: ' + D.ROWS_T_WHY
-        self.stats = dict(eng.stats.as_dict(), engine=engine, per_trajectory=True,
+        self.stats = dict(eng.stats.as_dict(), engine=engine, per_trajectory=True, **({'kernel': 'k_rows_mlp'} if route.kind == 'fused_rows_mlp' else {}),
                           rows={'n_attempts': rows[:, 0], 'n_accepted': rows[:, 1], 'nfe': rows[:, 2], 'status': rows[:, 3]})
         if bits:
             bad = torch.nonzero(rows[:, 3]).flatten().tolist()
@@ -946,7 +971,7 @@ class _AdaptiveRKSolver(AdaptiveStepsizeODESolver):
         return (out,)
 
     def _integrate_on(self, route, t):
-        if route.kind == 'fused_rows':
+        if route.kind in ('fused_rows', 'fused_rows_mlp'):
             return self._integrate_rows(route, t)
         fused = route.kind in ('fused', 'fused_tuple', 'fused_coop')
         eng = self._make_engine(route) if fused else None
